@@ -7,8 +7,18 @@ of the batch (Token.encrypt, Token.py:87-97) followed by verify+decrypt of the
 tokens it produced (Token.decrypt, Token.py:100-114).  Inputs are generated on
 the device before timing (synthetic, uniform random bytes).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run does what the headline needs and no more: set up the batch, check
+one round trip of it, warm up, time K steps, print the line.  --full adds every
+other measurement of the line (the other HBM layout, aligned slots, the
+in-run clock's stamped pass, the host-origin and composed-interface paths, the
+8-GPU rank shares, c3, per-call threads, the CPU baselines and, at N > 1, the
+host-origin aggregate and the sharded c4 pass); without it those fields are
+null.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs below); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 Multi-GPU: packets are independent, so each rank owns its own 2^20-packet
 shard (weak scaling) and no collective touches the data path; RCCL is used
@@ -20,8 +30,8 @@ the whole batch (c4: 262 144 x 16 KiB Resource chunks, one key; c5: 8 M
 packets of 64 B-4 KiB, 65 536 keys, half encrypted and half decrypted), and
 shard.sharded_call moves each rank its share over RCCL (xGMI), runs the
 kernels, and gathers the outputs back; scatter, compute and gather are timed
-separately.  With N > 1 the default c2 run also makes one
-sharded c4 pass and reports it under "sharded_c4".
+separately.  With N > 1 the default c2 run with --full also
+makes one sharded c4 pass and reports it under "sharded_c4".
 """
 import argparse
 import json
@@ -93,7 +103,16 @@ def parse():
     ap.add_argument("--no-e2e", dest="e2e", action="store_false")
     ap.add_argument("--no-node", dest="node", action="store_false",
                     help="skip the composed interface path (reticulum_amd.pipeline) at N = 1")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (other layout, aligned slots, stamped clock "
+                         "pass, host-origin and interface paths, rank shares, c3, per-call threads, CPU baselines; "
+                         "N > 1: host-origin aggregate and sharded c4); the options above that skip one apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (c2 / c3 steps) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def warmup(step, stream, min_steps, min_seconds):
@@ -115,6 +134,73 @@ def warmup(step, stream, min_steps, min_seconds):
         prev = ev
     torch.cuda.synchronize()
     return n, time.perf_counter() - t0
+
+
+DUMP_SEED = 20250
+DUMP_MAX_PACKETS = 1 << 20      # per-packet vectors: whole up to this many packets, else a seeded sample
+DUMP_ROW_BYTES = 24_000_000     # float32 bytes given to the sampled token + plaintext rows
+
+
+def _seeded_rows(n, k, seed):
+    """``k`` of ``n`` row numbers, sorted, the first and the last row among
+    them; the same for every run with the same ``n`` and ``k``."""
+    import numpy as np
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    idx = np.random.Generator(np.random.PCG64(seed)).choice(n, size=k, replace=False)
+    idx[:2] = (0, n - 1)
+    return np.unique(idx).astype(np.int64)
+
+
+def capture_outputs(tok, back, out_len, status, L):
+    """What a caller of the timed step receives, taken on the device right
+    after the last timed step (queued GPU work only; dump_outputs writes it):
+    * out_len, status: the decrypt's per-packet length and status;
+    * token_row_sums, plaintext_row_sums: the byte sum of every packet's token
+      and of its decrypted plaintext (float64, exact);
+    * tokens, plaintexts: whole rows of a seeded sample of packets, one byte
+      per element, with their packet numbers in sample_rows.
+    Past DUMP_MAX_PACKETS packets the per-packet vectors cover a seeded sample
+    too (packet_rows).  Sizes are bounded by the constants above: under 64 MB
+    in all for any batch."""
+    import torch
+    n, tl = tok.shape
+    dev = tok.device
+    out = {}
+    pk = _seeded_rows(n, DUMP_MAX_PACKETS, DUMP_SEED)
+    pk_d = None
+    if len(pk) < n:
+        pk_d = torch.from_numpy(pk).to(dev)
+        out["packet_rows"] = pk_d.to(torch.float64)
+    pick = (lambda v: v) if pk_d is None else (lambda v: v.index_select(0, pk_d))
+    out["out_len"] = pick(out_len).to(torch.float32)
+    out["status"] = pick(status).to(torch.float32)
+    out["token_row_sums"] = pick(tok.sum(dim=1, dtype=torch.int64)).to(torch.float64)
+    out["plaintext_row_sums"] = pick(back[:, :L].sum(dim=1, dtype=torch.int64)).to(torch.float64)
+    rows = _seeded_rows(n, max(2, DUMP_ROW_BYTES // (4 * (tl + L))), DUMP_SEED + 1)
+    rows_d = torch.from_numpy(rows).to(dev)
+    out["sample_rows"] = rows_d.to(torch.float64)
+    out["tokens"] = tok.index_select(0, rows_d).to(torch.float32)
+    out["plaintexts"] = back[:, :L].index_select(0, rows_d).to(torch.float32)
+    return out
+
+
+def dump_outputs(directory, captured):
+    """Write capture_outputs' arrays as ``directory``/<name>.npy (float32 /
+    float64); returns their shapes and the bytes written for the line."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    shapes, total = {}, 0
+    for name, t in captured.items():
+        a = t.cpu().numpy()
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        shapes[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        total += a.nbytes
+    return {"arrays": shapes, "bytes": total,
+            "note": "outputs of the last timed step of the headline layout (bench.capture_outputs): per-packet "
+                    "out_len, status and byte sums of every token and plaintext, whole token and plaintext rows "
+                    "of a seeded sample of packets (sample_rows)"}
 
 
 def cpu_baseline(seconds, workers, L):
@@ -254,6 +340,8 @@ def main():
     from reticulum_amd import _native, device
 
     if args.config in ("c4", "c5"):
+        if args.dump_outputs:
+            raise SystemExit("bench: --dump-outputs covers the token steps (c2 / c3), not the sharded configs")
         res = sharded_bench(args.config, args, world, rank, local, reps=args.sharded_reps)
         if rank == 0:
             print(json.dumps(res))
@@ -290,10 +378,15 @@ def main():
     # wave load/store one contiguous KiB: north_star's "coalesced HBM loads
     # across the packet batch").  Tokens and plaintexts are identical in both
     # (checked below); --layout picks the one the headline value is timed on,
-    # the other is timed right after it in the same run.
-    pt_u = device.interleave(pt, L)
-    tok_u = torch.empty((tl // 16, n, 16), dtype=torch.uint8, device=dev)
-    back_u = torch.empty(((tl - 48) // 16, n, 16), dtype=torch.uint8, device=dev)
+    # the other is timed right after it in the same run (--full only).
+    layouts = [args.layout]
+    if args.full and not args.one_layout:
+        layouts += [x for x in ("interleaved", "rows") if x != args.layout]
+    pt_u = tok_u = back_u = None
+    if "interleaved" in layouts:
+        pt_u = device.interleave(pt, L)
+        tok_u = torch.empty((tl // 16, n, 16), dtype=torch.uint8, device=dev)
+        back_u = torch.empty(((tl - 48) // 16, n, 16), dtype=torch.uint8, device=dev)
 
     def make_step(layout):
         ilv = layout == "interleaved"
@@ -315,7 +408,6 @@ def main():
                 ev[2].record(stream)
         return step
 
-    layouts = [args.layout] + ([] if args.one_layout else [x for x in ("interleaved", "rows") if x != args.layout])
     steps = {lay: make_step(lay) for lay in layouts}
     # correctness gate on the benchmarked data (size-independent properties),
     # before the warmup so that nothing idles the GPU between warmup and timing
@@ -333,7 +425,8 @@ def main():
     # plaintext rows starting on a cache line): a caller-side layout choice
     # (DESIGN.md §4.9).  Same kernels, same bytes; timed after the headline.
     aligned_step = None
-    if args.aligned and not args.one_layout and args.layout == "rows" and ps == L and ts == tl and args.tok_offset == 0:
+    if (args.full and args.aligned and not args.one_layout and args.layout == "rows"
+            and ps == L and ts == tl and args.tok_offset == 0):
         pt_a = device.aligned_rows(n, L, 0, dev)          # plaintext rows on lines
         pt_a.copy_(pt)
         tok_a = device.aligned_rows(n, tl, 16, dev)       # each token's ciphertext on a line
@@ -355,13 +448,15 @@ def main():
                 and torch.equal(tok_a, tok)):
             raise SystemExit("bench: round trip failed on the aligned-slot batch")
 
-    def timed(step):
+    def timed(step, after=None):
         """The timed steps run unstamped (stamping adds a
         workgroup barrier and four atomics per workgroup to every launch);
-        the in-run clock comes from a stamped pass of the same steps right
-        after them, whose elapsed time is reported beside the headline's."""
+        with --full the in-run clock comes from a stamped pass of the same
+        steps right after them, whose elapsed time is reported beside the
+        headline's.  ``after`` runs between the two (it may only queue GPU
+        work: the outputs of the last timed step are still in place)."""
         evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
-        clock = device.LaunchClock(dev)      # the stamped pass (rt_clock_stamps)
+        clock = device.LaunchClock(dev) if args.full else None      # the stamped pass (rt_clock_stamps)
         if world > 1:
             dist.barrier()
         warm = warmup(step, stream, args.warmup, args.warmup_seconds)
@@ -373,12 +468,15 @@ def main():
             step(evs[k])
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        with clock:
-            t2 = time.perf_counter()
-            for k in range(args.steps):
-                step()
-            torch.cuda.synchronize()
-            t3 = time.perf_counter()
+        if after is not None:
+            after()
+        if clock is not None:
+            with clock:
+                t2 = time.perf_counter()
+                for k in range(args.steps):
+                    step()
+                torch.cuda.synchronize()
+                t3 = time.perf_counter()
         if world > 1:
             dist.barrier()
         el = t1 - t0
@@ -389,6 +487,8 @@ def main():
             t = torch.tensor([el, e_avg, d_avg], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el, e_avg, d_avg = t.tolist()
+        if clock is None:
+            return el, e_avg, d_avg, e_ms, d_ms, warm, {"note": "no stamped pass in this run (bench.py --full)"}
         clk = clock.summary()
         clk["stamped_pass_ms_per_step"] = (t3 - t2) / args.steps * 1e3
         clk["unstamped_ms_per_step"] = (t1 - t0) / args.steps * 1e3
@@ -396,7 +496,16 @@ def main():
                        "stamped_pass_ms_per_step vs unstamped_ms_per_step is the stamps' cost on this box")
         return el, e_avg, d_avg, e_ms, d_ms, warm, clk
 
-    elapsed, enc_avg, dec_avg, enc_ms, dec_ms, (warm_steps, warm_s), clk = timed(steps[layouts[0]])
+    captured = {}
+    capture = None
+    if args.dump_outputs and rank == 0:
+        def capture():
+            if layouts[0] == "interleaved":
+                rows = device.deinterleave(tok_u, tl), device.deinterleave(back_u, tl - 48)
+            else:
+                rows = tok, back
+            captured.update(capture_outputs(rows[0], rows[1], out_len, status, L))
+    elapsed, enc_avg, dec_avg, enc_ms, dec_ms, (warm_steps, warm_s), clk = timed(steps[layouts[0]], capture)
     other = None
     if len(layouts) == 2:
         el2, e2, d2, _, _, _, clk2 = timed(steps[layouts[1]])
@@ -417,9 +526,9 @@ def main():
     # PCIe-inclusive (host buffers, pinned) rate for DESIGN.md: every rank at
     # once on its own shard, over its own PCIe link (the node's host-origin rate)
     # (N > 1: below, after the headline line exists, under a deadline)
-    e2e = e2e_rate(ks, pt, iv, L, tl, n, stream) if args.e2e and world == 1 else None
+    e2e = e2e_rate(ks, pt, iv, L, tl, n, stream) if args.full and args.e2e and world == 1 else None
     node = shard8 = c5share = c3leg = percall = None
-    if args.node and world == 1 and args.config == "c2":
+    if args.full and args.node and world == 1 and args.config == "c2":
         try:
             node = node_rate(dev)
         except Exception as exc:          # never fatal for the headline
@@ -465,8 +574,8 @@ def main():
 
     # the CPU baselines run on rank 0 at N = 1 here; at N > 1 after the sharded
     # pass, while the other ranks wait idle (below)
-    cpu = cpu_baseline(args.cpu_seconds, args.cpu_workers, L) if world == 1 else None
-    cpu_ssl = cpu_openssl(min(args.cpu_seconds, 5.0), args.cpu_workers, L) if world == 1 else None
+    cpu = cpu_baseline(args.cpu_seconds, args.cpu_workers, L) if args.full and world == 1 else None
+    cpu_ssl = cpu_openssl(min(args.cpu_seconds, 5.0), args.cpu_workers, L) if args.full and world == 1 else None
     pkts_total = n * world * args.steps
     value = pkts_total / elapsed
     if key_setup is not None:
@@ -483,6 +592,7 @@ def main():
         "gib_s": value * L / 2**30,
         "n_gpus": world,
         "steps": args.steps,
+        "full": args.full,
         "warmup": args.warmup,
         "warmup_run": {"steps": warm_steps, "seconds": warm_s,
                        "note": "untimed steps actually run before the timed region: at least --warmup, continued "
@@ -566,6 +676,8 @@ def main():
         "per_call_threads": percall,
         "sharded_c4": None,
     }
+    if captured:
+        line["dumped_outputs"] = dump_outputs(args.dump_outputs, captured)
 
     # c4 sharded over the same ranks (scatter / kernels / gather over RCCL):
     # the xGMI legs of SURVEY §8(e), measured beside the weak-scaling headline.
@@ -574,7 +686,7 @@ def main():
     # point-to-point transfer) makes rank 0 print the line with the error and
     # every rank exit, before the process group's own 300 s timeout would
     # abort the job without a line.
-    if world > 1 and args.e2e:
+    if world > 1 and args.full and args.e2e:
         # every rank's host-origin path at once; a stuck barrier or reduction
         # here must not cost the headline line either
         guard = _LineGuard(line if rank == 0 else None, 120.0, field="e2e_pcie", what="host-origin pass")
@@ -584,7 +696,7 @@ def main():
         except Exception as e:  # reported, never fatal for the headline line
             line["e2e_pcie"] = {"error": f"{type(e).__name__}: {e}"}
         guard.finish()
-    if world > 1 and os.environ.get("RNSTOK_BENCH_SHARDED", "1") != "0":
+    if world > 1 and args.full and os.environ.get("RNSTOK_BENCH_SHARDED", "1") != "0":
         guard = _LineGuard(line if rank == 0 else None, args.sharded_timeout)
         try:
             line["sharded_c4"] = sharded_bench("c4", args, world, rank, local, reps=2)
@@ -594,7 +706,7 @@ def main():
         guard.finish()
     elif world > 1:
         dist.barrier()
-    if world > 1:
+    if world > 1 and args.full:
         # north_star: the reference path timed on the same box's host cores in
         # the same run, at every N.  Rank 0 runs it after the GPU work; the
         # other ranks block on the rendezvous store (a socket read, no spinning

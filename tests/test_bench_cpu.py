@@ -167,6 +167,61 @@ def test_committed_n_gt_1_lines_carry_every_north_star_number():
             assert ph["pipelined_equals_serial"] is True and ph["pipelined_chunks"] >= 1
 
 
+def test_dump_outputs_arrays_are_seeded_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: capture_outputs takes the per-packet vectors whole (a
+    seeded sample past DUMP_MAX_PACKETS) and whole rows of a seeded sample of
+    packets; dump_outputs writes them as float32 / float64 .npy files.  Two
+    calls on the same batch write identical files."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, L = 1001, 37
+    tl = 16 + 16 * (L // 16 + 1) + 32
+    g = torch.Generator().manual_seed(9)
+    tok = torch.randint(0, 256, (n, tl), dtype=torch.uint8, generator=g)
+    back = torch.randint(0, 256, (n, tl - 48), dtype=torch.uint8, generator=g)
+    out_len = torch.full((n,), L, dtype=torch.int32)
+    status = torch.zeros(n, dtype=torch.int32)
+    status[5] = 2
+    monkeypatch.setattr(bench, "DUMP_ROW_BYTES", 4 * (tl + L) * 100)       # 100 of the 1001 rows
+    info = bench.dump_outputs(str(tmp_path / "a"), bench.capture_outputs(tok, back, out_len, status, L))
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(got) == set(info["arrays"]) == {"out_len", "status", "token_row_sums", "plaintext_row_sums",
+                                               "sample_rows", "tokens", "plaintexts"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert info["bytes"] == sum(a.nbytes for a in got.values())
+    rows = got["sample_rows"].astype(np.int64)
+    assert 98 <= len(rows) <= 100 and rows[0] == 0 and rows[-1] == n - 1 and (np.diff(rows) > 0).all()
+    assert np.array_equal(got["tokens"], tok.numpy()[rows]) and got["tokens"].shape == (len(rows), tl)
+    assert np.array_equal(got["plaintexts"], back.numpy()[rows, :L])
+    assert np.array_equal(got["status"], status.numpy()) and np.array_equal(got["out_len"], out_len.numpy())
+    assert np.array_equal(got["token_row_sums"], tok.numpy().astype(np.int64).sum(1))
+    assert np.array_equal(got["plaintext_row_sums"], back.numpy()[:, :L].astype(np.int64).sum(1))
+    # the same batch again: the same sample, the same files
+    bench.dump_outputs(str(tmp_path / "b"), bench.capture_outputs(tok, back, out_len, status, L))
+    for name, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy")))
+    # past DUMP_MAX_PACKETS the per-packet vectors cover a seeded sample, named in packet_rows
+    monkeypatch.setattr(bench, "DUMP_MAX_PACKETS", 64)
+    cap = bench.capture_outputs(tok, back, out_len, status, L)
+    pk = cap["packet_rows"].numpy().astype(np.int64)
+    assert 62 <= len(pk) <= 64 and cap["status"].shape == (len(pk),)
+    assert np.array_equal(cap["status"].numpy(), status.numpy()[pk])
+    assert np.array_equal(cap["token_row_sums"].numpy(), tok.numpy().astype(np.int64).sum(1)[pk])
+
+
+def test_dump_budget_at_the_benchmark_shapes():
+    """The dump stays under 64 MB for the c2 batch and for any larger one."""
+    sys.path.insert(0, ROOT)
+    import bench
+    for n, L in ((1 << 20, 500), (8 << 20, 4096), (1 << 22, 16)):
+        tl = 16 + 16 * (L // 16 + 1) + 32
+        per_packet = min(n, bench.DUMP_MAX_PACKETS) * (4 + 4 + 8 + 8 + (8 if n > bench.DUMP_MAX_PACKETS else 0))
+        k = min(n, max(2, bench.DUMP_ROW_BYTES // (4 * (tl + L))))
+        assert per_packet + k * (4 * (tl + L) + 8) <= 64_000_000
+
+
 def test_ceiling_fracs_and_calibrated_traffic():
     """Round 6: the bench line's ceiling fractions (canonical lane-ops over the
     ISA slot floor at two wave64 instructions per slot) and the decrypt's

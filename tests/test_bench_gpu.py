@@ -26,6 +26,48 @@ def test_sharded_config_world1(cfg, packets):
     assert rep["roofline"]["bound"] == "valu" and 0 < rep["roofline"]["frac"] < 1
 
 
+def test_plain_run_line_and_dumped_outputs(tmp_path, monkeypatch, capsys):
+    """A plain run (no --full) times exactly --steps steps, prints one line
+    with the headline fields and leaves every other measurement null; its
+    --dump-outputs arrays are the last timed step's outputs: tokens equal to
+    the oracle's for the seeded inputs, plaintexts equal to the inputs."""
+    import json
+    import sys
+    import numpy as np
+    import torch
+    import bench
+    from oracle import ctoken as oracle
+    n, L, steps = 3001, 37, 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                                      "--warmup-seconds", "0", "--packets", str(n), "--length", str(L),
+                                      "--dump-outputs", str(tmp_path / "out")])
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["metric"] == bench.BASELINE_METRIC and rec["higher_is_better"] is True and rec["full"] is False
+    assert rec["steps"] == steps and rec["ms_per_step"] > 0 and rec["dtype"] == "u8/u32 (integer)"
+    assert abs(rec["value"] - n / (rec["ms_per_step"] * 1e-3)) <= 1e-6 * rec["value"]
+    for moved in ("cpu_baseline", "cpu_openssl", "other_layout", "aligned_rows", "e2e_pcie", "node_pipeline",
+                  "c4_rank_share_8gpu", "c5_rank_share_8gpu", "c3_per_key", "per_call_threads", "sharded_c4"):
+        assert rec[moved] is None, moved
+    assert rec["roofline"]["clock_ghz"] is None              # no stamped pass
+    got = {name: np.load(tmp_path / "out" / (name + ".npy")) for name in rec["dumped_outputs"]["arrays"]}
+    assert (got["status"] == 0).all() and (got["out_len"] == L).all() and got["status"].shape == (n,)
+    # the inputs as bench.main seeds them
+    g = torch.Generator(device="cuda").manual_seed(1000)
+    pt = torch.randint(0, 256, (n, L), dtype=torch.uint8, device="cuda", generator=g).cpu().numpy()
+    iv = torch.randint(0, 256, (n, 16), dtype=torch.uint8, device="cuda", generator=g).cpu().numpy()
+    key = torch.randint(0, 256, (1, 64), dtype=torch.uint8, generator=torch.Generator().manual_seed(7)).numpy()[0]
+    rows = got["sample_rows"].astype(np.int64)
+    assert len(rows) == n and np.array_equal(got["plaintexts"], pt)
+    assert np.array_equal(got["plaintext_row_sums"], pt.astype(np.int64).sum(1))
+    assert np.array_equal(got["token_row_sums"], got["tokens"].astype(np.int64).sum(1))
+    for i in range(0, n, 97):
+        want = np.frombuffer(oracle.encrypt(key.tobytes(), iv[i].tobytes(), pt[i].tobytes()), dtype=np.uint8)
+        assert np.array_equal(got["tokens"][i], want), i
+
+
 def test_c3_key_setup_times():
     """the per-key setup timed apart from the steps, from a
     host table and from a table already in HBM."""

@@ -16,7 +16,7 @@ for args in "${CS[@]}"; do
 done
 grep -v amdgpu.ids $O/ab.txt
 [ -n "$NO_PMC" ] && exit 0
-BASE="--steps 30 --warmup 2 --cpu-seconds 0 --no-e2e --no-node --one-layout --no-aligned $BENCH_ARGS"
+BASE="--full --steps 30 --warmup 2 --cpu-seconds 0 --no-e2e --no-node --one-layout --no-aligned $BENCH_ARGS"
 for v in "$@"; do
   IFS=';' read -ra PS <<< "${PMC_PASSES:-FETCH_SIZE;WRITE_SIZE;GRBM_GUI_ACTIVE GRBM_COUNT}"
   for PASS in "${PS[@]}"; do

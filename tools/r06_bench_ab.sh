@@ -7,7 +7,7 @@ set -o pipefail
 TAG=$1; R=$2; shift 2
 O=gpurun_out/$TAG
 mkdir -p $O
-B="--steps 40 --warmup 2 --cpu-seconds 0 --no-e2e --no-node --one-layout --no-aligned $BENCH_ARGS"
+B="--full --steps 40 --warmup 2 --cpu-seconds 0 --no-e2e --no-node --one-layout --no-aligned $BENCH_ARGS"
 for r in $(seq 1 $R); do
   for v in "$@"; do
     RNSTOK_LIB=exp_ship/$v/librnstok.so timeout -k 10 200 python bench.py $B > $O/${v}_$r.json 2> $O/${v}_$r.err || { tail -5 $O/${v}_$r.err; exit 1; }

@@ -4,7 +4,7 @@
 set -o pipefail
 O=gpurun_out/${PERKEY_TAG:-r06q}
 mkdir -p $O
-B="--steps 40 --warmup 2 --cpu-seconds 0 --no-e2e --no-node --one-layout --no-aligned --keys 65536"
+B="--full --steps 40 --warmup 2 --cpu-seconds 0 --no-e2e --no-node --one-layout --no-aligned --keys 65536"
 for r in 1 2; do
   for v in "$@"; do
     RNSTOK_LIB=exp_ship/$v/librnstok.so timeout -k 10 200 python bench.py $B > $O/c3_${v}_$r.json 2> $O/c3_${v}_$r.err || { tail -5 $O/c3_${v}_$r.err; exit 1; }

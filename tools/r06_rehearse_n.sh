@@ -6,7 +6,7 @@ O=gpurun_out/r06_rehearse
 mkdir -p $O
 for N in 4 8; do
   RNSTOK_BENCH_REHEARSE=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-    --master-addr 127.0.0.1 --master-port $((29700 + N)) bench.py --gpus $N --steps 5 --warmup 2 --cpu-seconds 2 \
+    --master-addr 127.0.0.1 --master-port $((29700 + N)) bench.py --full --gpus $N --steps 5 --warmup 2 --cpu-seconds 2 \
     > $O/n$N.json 2> $O/n$N.err || { echo "rehearse n$N failed"; tail -30 $O/n$N.err; exit 1; }
   python3 - $O/n$N.json $N <<'PY'
 import json, sys
