@@ -317,23 +317,14 @@ hipError_t launch_hkdf(const HkdfArgs &a, hipStream_t s) {
     const auto aligned4 = [](const uint8_t *p, uint64_t stride) { return (((uintptr_t)p | stride) & 3u) == 0; };
     const bool fast = a.context_len == 0 && a.ikm_len % 4u == 0 && a.ikm_len <= 52u && aligned4(a.ikm, a.ikm_stride) &&
                       (a.salt == nullptr || (a.salt_len % 4u == 0 && a.salt_len <= 64u && aligned4(a.salt, a.salt_stride)));
-#ifdef RNSTOK_NO_FAST_HKDF
-    const bool use_fast = false && fast;
-#else
-    const bool use_fast = fast;
-#endif
     // a shared salt row: 1024 x 256 lanes (4 waves per SIMD on 256 CUs), each
     // computing the salt's midstates once for its n / 262144 keys
-#ifdef RNSTOK_NO_SHARED_SALT
-    const bool shared = false;
-#else
     const bool shared = a.salt != nullptr && a.salt_stride == 0 && a.n > 1;
-#endif
     const uint64_t blocks = ((uint64_t)a.n + threads - 1) / threads;
     const dim3 grid((unsigned)(shared && blocks > 1024u ? 1024u : blocks));
-    if (use_fast && shared)
+    if (fast && shared)
         hipLaunchKernelGGL((k_hkdf<true, true>), grid, dim3(threads), 0, s, a);
-    else if (use_fast)
+    else if (fast)
         hipLaunchKernelGGL((k_hkdf<true, false>), grid, dim3(threads), 0, s, a);
     else if (shared)
         hipLaunchKernelGGL((k_hkdf<false, true>), grid, dim3(threads), 0, s, a);
@@ -342,22 +333,16 @@ hipError_t launch_hkdf(const HkdfArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-#ifndef RNSTOK_FUSED_BLOCKS_PER_CU
-#define RNSTOK_FUSED_BLOCKS_PER_CU 3      // 48 KiB of staging and 132 VGPRs: 3 workgroups of 4 waves per CU
-#endif
+constexpr uint64_t FUSED_BLOCKS_PER_CU = 3;   // 48 KiB of staging and 132 VGPRs: 3 workgroups of 4 waves per CU
 hipError_t launch_hkdf_key_setup(const HkdfArgs &a, const uint8_t *sbox, uint32_t *rec, int n_cu, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
-#ifdef RNSTOK_NO_FUSED_HKDF          // A/B: the two-launch path
-    return hipErrorNotSupported;
-#endif
     const auto aligned4 = [](const uint8_t *p, uint64_t stride) { return (((uintptr_t)p | stride) & 3u) == 0; };
     const bool fast = a.context_len == 0 && a.ikm_len % 4u == 0 && a.ikm_len <= 52u && aligned4(a.ikm, a.ikm_stride) &&
                       (a.salt == nullptr || (a.salt_len % 4u == 0 && a.salt_len <= 64u && aligned4(a.salt, a.salt_stride)));
     if (!fast || (a.length != 64u && a.length != 32u)) return hipErrorNotSupported;
     const bool shared = a.salt != nullptr && a.salt_stride == 0 && a.n > 1;
     uint64_t blocks = ((uint64_t)a.n + 255u) / 256u;
-    if (shared && blocks > (uint64_t)RNSTOK_FUSED_BLOCKS_PER_CU * (uint64_t)n_cu)
-        blocks = (uint64_t)RNSTOK_FUSED_BLOCKS_PER_CU * (uint64_t)n_cu;
+    if (shared && blocks > FUSED_BLOCKS_PER_CU * (uint64_t)n_cu) blocks = FUSED_BLOCKS_PER_CU * (uint64_t)n_cu;
     const dim3 grid((unsigned)blocks);
     if (a.length == 64u) {
         if (shared)

@@ -29,10 +29,7 @@ __device__ __forceinline__ uint32_t sub_word(const uint8_t *sb, uint32_t w) {
 // 544-B lane stride, so a direct store instruction would touch 64 lines; each
 // wave stages KS_P pieces of its 64 records per round and stores them as runs
 // of KS_P * 16 contiguous bytes.  Records of consecutive keys are adjacent.
-#ifndef RNSTOK_KS_P
-#define RNSTOK_KS_P 12
-#endif
-constexpr int KS_P = RNSTOK_KS_P, KS_PIECES = REC_WORDS / 4, KS_ROUNDS = (KS_PIECES + KS_P - 1) / KS_P;
+constexpr int KS_P = 12, KS_PIECES = REC_WORDS / 4, KS_ROUNDS = (KS_PIECES + KS_P - 1) / KS_P;
 constexpr int KS_STAGE_PIECES = 64 * KS_P;     // per wave
 
 // Lanes of one wave exchange data through LDS: order the wave's LDS writes

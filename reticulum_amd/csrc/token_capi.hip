@@ -42,10 +42,7 @@ struct Stager {
 // one thread unchanged at 19 000); streams beyond the box's four hardware
 // queues still overlap the host-side waits of concurrent calls.  Pinned
 // staging grows on demand, at most 8 MiB per lane.
-#ifndef RNSTOK_N_STAGERS
-#define RNSTOK_N_STAGERS 8
-#endif
-static constexpr int N_STAGERS = RNSTOK_N_STAGERS;
+static constexpr int N_STAGERS = 8;
 
 // Chunk counters for the token kernels' dynamic packet loop (ragged uniform
 // batches): one 64-B slot per launch.  A slot is handed out again only after
@@ -244,9 +241,7 @@ static uint8_t *stage(Stager &g, uint64_t bytes);
 // 38.6 us, 19 100 -> 21 800 calls/s (three runs each,
 // profiles/r06_host_direct_ab.txt).  Batches keep the copies (their kernels
 // would read every packet across PCIe; not measured).
-#ifndef RNSTOK_HOST_DIRECT
-#define RNSTOK_HOST_DIRECT 1
-#endif
+static bool host_direct(const uint8_t *staged, uint32_t n) { return staged && n == 1; }
 
 // A key set whose records are allocated and built on stream s.  `build`
 // enqueues the kernel(s) that write k->d_rec.
@@ -734,7 +729,7 @@ int rt_encrypt_host(const rt_keyset *k, const uint8_t *pt, const uint64_t *pt_of
     hipStream_t s = g.stream;
     const bool gaps = tok_sum != tok_ext;   // gaps between tokens: keep the caller's bytes there
     uint8_t *h = stage(g, total);
-    const bool direct = RNSTOK_HOST_DIRECT && h && n == 1;
+    const bool direct = host_direct(h, n);
     if (h) {
         if (pt_ext) memcpy(h + o_pt, pt, pt_ext);
         memcpy(h + o_iv, iv, 16ull * n);
@@ -803,7 +798,7 @@ int rt_decrypt_host(const rt_keyset *k, const uint8_t *tok, const uint64_t *tok_
     hipStream_t s = g.stream;
     const bool gaps = pt_ext && pt_sum != pt_ext;   // gaps between plaintexts: keep the caller's bytes there
     uint8_t *h = stage(g, total);
-    const bool direct = RNSTOK_HOST_DIRECT && h && n == 1;
+    const bool direct = host_direct(h, n);
     if (h) {
         if (tok_ext) memcpy(h + o_tok, tok, tok_ext);
         memcpy(h + o_to, tok_off, 8ull * n);

@@ -22,73 +22,13 @@
 namespace rnstok {
 
 // Workgroup sizes: one workgroup per CU (the LDS table image is 128/160 KiB).
-// Packed rows: 16-B units at a 560-B row stride share 128-B lines between
-// consecutive quads, and one quad apart the line has left L2 (profiles/r04o,
-// r04p, r04q, one-process A/Bs at c2 / 1500 B / packed):
-#ifndef RNSTOK_ENC_PAIR              // split encrypt, plaintext quads loaded in pairs: fetch -13 %, time -0.5 %
-#define RNSTOK_ENC_PAIR 1
-#endif
-// (split encrypt, token quads stored in pairs: writes -22 %, time +2.2 %: not adopted, r04q)
-#ifndef RNSTOK_SPLIT_TILE            // experiment: packed split encrypt reads 64-packet plaintext tiles
-#define RNSTOK_SPLIT_TILE 0
-#endif
-#ifndef RNSTOK_DEC_TAG_EARLY         // decrypt: tag units loaded before the quad loop
-#define RNSTOK_DEC_TAG_EARLY 1
-#endif
-#ifndef RNSTOK_DEC_PAIR              // decrypt, one key, token quads loaded in pairs: fetch -21 %, time -1.6 %
-#define RNSTOK_DEC_PAIR 1
-#endif
-// Split encrypt, packed rows: the ciphertext units of a 64-B sector that a quad
-// shares with the next quad are held and stored with the next quad's, so every
-// sector leaves in one burst of stores (fabric write requests 18.3 M -> 12.8 M
-// per c2 launch, the count of the same tokens with their ciphertext on lines).
-// The chip then holds a higher clock: whole-bench A/Bs (each variant its own
-// sustained run) c2 +2.2 % (2.20 -> 2.25 GHz, cycles equal), per-packet keys
-// c3 encrypt -2.9 %, c5's encrypt half -4.7 % (profiles/r06_clock_ab/).  An A/B
-// that interleaves the variants launch by launch shares one clock between
-// them and showed +1.3 %.
-#ifndef RNSTOK_ENC_ST_SECTOR
-#define RNSTOK_ENC_ST_SECTOR 1
-#endif
-#ifndef RNSTOK_ENC_ST_SECTOR_PERKEY  // per-packet keys: with single plaintext quads (next line) 5 VGPRs
-#define RNSTOK_ENC_ST_SECTOR_PERKEY 1  // spilled; with the paired loads 31
-#endif
-#ifndef RNSTOK_ENC_PAIR_PERKEY       // per-packet keys: plaintext quads loaded in pairs (off: the
-#define RNSTOK_ENC_PAIR_PERKEY 0     // registers go to the held sector units)
-#endif
-#ifndef RNSTOK_SPLIT_DYN              // split encrypt: unevenly divided uniform batches from a counter
-#define RNSTOK_SPLIT_DYN 1
-#endif
-#ifndef RNSTOK_SPLIT_DYN_MIN_LEN
-#define RNSTOK_SPLIT_DYN_MIN_LEN 256u
-#endif
-#ifndef RNSTOK_DEC1024_MAX_TOKEN     // uniform tokens up to this length: the 1024-thread decrypt
-#define RNSTOK_DEC1024_MAX_TOKEN 320u  // (plaintexts up to 271 B)
-#endif
-#ifndef RNSTOK_WG_ENC
-#define RNSTOK_WG_ENC 1024      // single key: 4 waves/SIMD, 128 VGPRs
-#endif
-#ifndef RNSTOK_WG_DEC
-#define RNSTOK_WG_DEC 768       // 3 waves/SIMD, no spills; with the chunk loop for c2's ragged
-                                // 5.33 packets per lane: 2 % faster than 1024 (A/B, 30 rounds)
-#endif
+constexpr int WG_ENC = 1024;      // single key: 4 waves/SIMD, 128 VGPRs
+constexpr int WG_DEC = 768;       // 3 waves/SIMD, no spills; with the chunk loop for c2's ragged
+                                  // 5.33 packets per lane: 2 % faster than 1024 (A/B, 30 rounds)
 // per-packet keys: the round keys live in VGPRs, so fewer waves per SIMD
-#ifndef RNSTOK_WG_PERKEY_ENC
-#define RNSTOK_WG_PERKEY_ENC 768   // <= 168 VGPRs, 3 waves/SIMD
-#endif
-#ifndef RNSTOK_WG_PERKEY_DEC
-#define RNSTOK_WG_PERKEY_DEC 768   // <= 168 VGPRs, 3 waves/SIMD (c3: 5.5 % faster than 512 threads
-                                   // at 256 VGPRs, despite some spilling; needs the chunk loop's balance)
-#endif
-constexpr int WG_ENC = RNSTOK_WG_ENC, WG_DEC = RNSTOK_WG_DEC;
-// Optional explicit occupancy target (waves per SIMD) for the single-key
-// kernels, so the scheduler may spend registers on loads in flight.
-#ifdef RNSTOK_WAVES_PER_EU
-#define RT_OCC __attribute__((amdgpu_waves_per_eu(RNSTOK_WAVES_PER_EU, RNSTOK_WAVES_PER_EU)))
-#else
-#define RT_OCC
-#endif
-constexpr int WG_PERKEY_ENC = RNSTOK_WG_PERKEY_ENC, WG_PERKEY_DEC = RNSTOK_WG_PERKEY_DEC;
+constexpr int WG_PERKEY_ENC = 768;   // <= 168 VGPRs, 3 waves/SIMD
+constexpr int WG_PERKEY_DEC = 768;   // <= 168 VGPRs, 3 waves/SIMD (c3: 5.5 % faster than 512 threads
+                                     // at 256 VGPRs, despite some spilling; needs the chunk loop's balance)
 
 // ------------------------------------------------------------ LDS tables --
 
@@ -271,7 +211,7 @@ __device__ __forceinline__ u32x4 pad_block(const uint8_t *p, uint32_t r) {
 // scattered 16-B pieces.  US is the distance between a
 // packet's consecutive units.
 template <int NR, bool PERKEY, bool ILV = false>
-__global__ RT_OCC __launch_bounds__(PERKEY ? WG_PERKEY_ENC : WG_ENC) void k_encrypt(EncArgs a) {
+__global__ __launch_bounds__(PERKEY ? WG_PERKEY_ENC : WG_ENC) void k_encrypt(EncArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tab_u32[];
     LaunchClock clk;
     clk.start(a.clk);
@@ -400,7 +340,7 @@ __global__ RT_OCC __launch_bounds__(PERKEY ? WG_PERKEY_ENC : WG_ENC) void k_encr
 //
 // Hand-over, two instances (A/B in one process against k_encrypt, tokens
 // identical, profiles/r04_split/r04f_three_way_ab.txt, r04h_enc_dec_split_ab.txt):
-// * packed rows (RB = false): an LDS ring after the 128 KiB table image, one
+// * packed rows (ILV = false): an LDS ring after the 128 KiB table image, one
 //   slot of one quad per lane (4 KiB per AES wave, 16-B unit j of lane l at
 //   1024 j + 16 l: conflict-free ds_write_b128 / ds_read_b128), which fills
 //   the CU's 160 KiB.  The two hand-over counters of each wave pair live in
@@ -409,7 +349,7 @@ __global__ RT_OCC __launch_bounds__(PERKEY ? WG_PERKEY_ENC : WG_ENC) void k_encr
 //   (-3.8 %) and 0.839 vs 0.886 (-5.3 %) on two boxes; 1500 B -2.5 / -3.1 %.
 //   Reading every lane's quad back from the token rows instead (a second
 //   scattered 16-B pattern) is 1.6 % slower at 500 B.
-// * interleaved (RB = true): no ring, every hashing lane reads its quad back
+// * interleaved (ILV = true): no ring, every hashing lane reads its quad back
 //   from the token buffer (coalesced 1-KiB reads, L2 hits, no LDS instruction
 //   taken from the lookups' pipe): 0.743 vs 0.814 ms (-8.8 %), 1500 B -9.6 %;
 //   the LDS ring there: -3.7 %.  (A staging ring in global memory instead of
@@ -426,10 +366,8 @@ __global__ RT_OCC __launch_bounds__(PERKEY ? WG_PERKEY_ENC : WG_ENC) void k_encr
 // keys (PERKEY: each AES lane loads its packet's round keys, each hashing lane
 // its ipad/opad midstates, from the 544-B key records; 128 VGPRs, 2 spilled
 // on rows).
-#ifndef RNSTOK_SPLIT_AES_WAVES       // AES waves (= hashing waves) per workgroup (experiment knob)
-#define RNSTOK_SPLIT_AES_WAVES 8
-#endif
-constexpr uint32_t SPLIT_AES_WAVES = RNSTOK_SPLIT_AES_WAVES, SPLIT_THREADS = 128u * RNSTOK_SPLIT_AES_WAVES;
+constexpr uint32_t SPLIT_AES_WAVES = 8;                           // AES waves (= hashing waves) per workgroup
+constexpr uint32_t SPLIT_THREADS = 128u * SPLIT_AES_WAVES;
 constexpr uint32_t SPLIT_RING = LDS_ENC_BYTES;                    // 8 x 4 KiB
 constexpr uint32_t LDS_ENC_SPLIT_BYTES = SPLIT_RING + SPLIT_AES_WAVES * 4096u;
 static_assert(LDS_ENC_SPLIT_BYTES <= 160u * 1024u, "LDS");
@@ -451,15 +389,7 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 // unit with the chunk's first quad; both run the chunk to its longest packet
 // (a length-ordered chunk is nearly uniform), each lane stopping at its own
 // last quad.  A chunk index past the batch tells the hashing wave to leave.
-#ifdef RNSTOK_SPLIT_PROBE
-// timing probe (probe builds only): per role, cycles spent waiting on the
-// other role, waits entered, cycles from the table fill to the end
-__device__ unsigned long long g_split_probe[8];
-#define SPLIT_PROBE(x) x
-#else
-#define SPLIT_PROBE(x)
-#endif
-template <int NR, bool ILV = false, bool RB = ILV, bool PERKEY = false, bool GEN = false>
+template <int NR, bool ILV = false, bool PERKEY = false, bool GEN = false>
 __global__ __launch_bounds__(SPLIT_THREADS) void k_encrypt_split(EncArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tab_u32[];
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
@@ -474,7 +404,6 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_encrypt_split(EncArgs a) {
     clk.start(a.clk);
     if (aes && lane < 3u) ((lds_u32 *)(uintptr_t)slot)[lane] = 0u;   // before the barrier
     fill_tables<false>(tab_u32, a.sbox, a.sbox + 256);     // ends with the workgroup barrier
-    SPLIT_PROBE(uint64_t pr_wait = 0; uint64_t pr_n = 0; const uint64_t pr_t0 = clock64();)
 
     const uint64_t US = ILV ? 16ull * a.n : 16ull;
     const uint32_t n_batches = (a.n + 63u) >> 6;
@@ -528,21 +457,32 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_encrypt_split(EncArgs a) {
             uint8_t *O = tok_at(p);
             u32x4 prev = valid ? ld16(a.iv + 16ull * p) : z;
             uint8_t *C = O + US;
-            // RNSTOK_ENC_ST_SECTOR (experiment): the ciphertext units of a 64-B
-            // sector that a quad shares with the next are stored together with
-            // the next quad's, so every sector is written by back-to-back stores
+            // Packed rows: the ciphertext units of a 64-B sector that a quad
+            // shares with the next quad are held and stored with the next
+            // quad's, so every sector leaves in one burst of stores (fabric
+            // write requests 18.3 M -> 12.8 M per c2 launch, the count of the
+            // same tokens with their ciphertext on lines).  The chip then
+            // holds a higher clock: whole-bench A/Bs (each variant its own
+            // sustained run) c2 +2.2 % (2.20 -> 2.25 GHz, cycles equal),
+            // per-packet keys c3 encrypt -2.9 %, c5's encrypt half -4.7 %
+            // (profiles/r06_clock_ab/).  An A/B that interleaves the variants
+            // launch by launch shares one clock between them and showed
+            // +1.3 %.
             // (sg: the sector phase of the lane's ciphertext start, in units)
-            constexpr bool SECT = !ILV && (PERKEY ? RNSTOK_ENC_ST_SECTOR_PERKEY : RNSTOK_ENC_ST_SECTOR);
+            constexpr bool SECT = !ILV;
             // (lane 0 stores at once: its hashing lane reads the quad back from the token buffer)
             const uint32_t sg = SECT && lane ? ((uint32_t)(uintptr_t)C >> 4) & 3u : 0u;
             u32x4 cp1 = z, cp2 = z;                        // the previous quad's units 1, 2 (unit 3: prev)
             if (valid && (!SECT || sg == 0u)) st16(O, prev);
-            // (experiment, RNSTOK_SPLIT_TILE: packed batches whose plaintexts a
-            // gather pass laid out as 64-packet tiles, unit u of lane l at
-            // pt_off + 1024 u; tokens stay byte strings)
-            const uint64_t USP = GEN && RNSTOK_SPLIT_TILE ? 1024ull : US;
-            // packed rows: full quads loaded in line-sharing pairs (k_decrypt)
-            constexpr bool PAIR = (PERKEY ? RNSTOK_ENC_PAIR_PERKEY : RNSTOK_ENC_PAIR) && !ILV;
+            // Packed rows, one key: full quads loaded in pairs (k_decrypt).
+            // 16-B units at a 560-B row stride share 128-B lines between
+            // consecutive quads, and one quad apart the line has left L2:
+            // fetch -13 %, time -0.5 % (profiles/r04o, r04p, r04q, one-process
+            // A/Bs at c2 / 1500 B / packed; token quads stored in pairs:
+            // writes -22 %, time +2.2 %, not adopted).  Per-packet keys load
+            // single quads, their registers go to the held sector units:
+            // 5 VGPRs spilled, with the paired loads 31.
+            constexpr bool PAIR = !PERKEY && !ILV;
             u32x4 nx[4];
             for (uint32_t q = 0; q <= wq; ++q) {
                 u32x4 x[4], c[4];
@@ -552,17 +492,17 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_encrypt_split(EncArgs a) {
                     for (int j = 0; j < 4; ++j) x[j] = nx[j];
                 } else if (q < nq) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) x[j] = valid ? ld16(P + USP * j) : z;
+                    for (int j = 0; j < 4; ++j) x[j] = valid ? ld16(P + US * j) : z;
                     if (PAIR && q + 1u < nq) {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) nx[j] = valid ? ld16(P + USP * (4 + j)) : z;
+                        for (int j = 0; j < 4; ++j) nx[j] = valid ? ld16(P + US * (4 + j)) : z;
                     }
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         x[j] = !act ? z
-                                    : ((uint32_t)j + 1u < tb ? ld16(P + USP * j)
-                                                             : ((uint32_t)j + 1u == tb ? pad_block(P + USP * j, rem) : z));
+                                    : ((uint32_t)j + 1u < tb ? ld16(P + US * j)
+                                                             : ((uint32_t)j + 1u == tb ? pad_block(P + US * j, rem) : z));
                 }
                 enc_quad<NR, false>(c, x, prev, K.rk, LN, S);
                 const uint32_t nst = q < nq ? 4u : tb;
@@ -588,18 +528,13 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_encrypt_split(EncArgs a) {
                         if ((uint32_t)j < nst) st16(C + US * j, c[j]);
                 }
                 prev = c[3];
-                P += 4 * USP;
+                P += 4 * US;
                 C += 4 * US;
                 // the slot is free once the hashing wave has taken every earlier quad
-                if (!RB && count) {
-                    SPLIT_PROBE(const uint64_t pw = clock64(); bool pwt = false;)
-                    while (__hip_atomic_load(consumed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < count) {
-                        SPLIT_PROBE(pwt = true;)
+                if (!ILV && count)
+                    while (__hip_atomic_load(consumed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < count)
                         __builtin_amdgcn_s_sleep(1);
-                    }
-                    SPLIT_PROBE(if (pwt) { pr_wait += clock64() - pw; ++pr_n; })
-                }
-                if (!RB && lane) {
+                if (!ILV && lane) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) mine[64 * j] = c[j];
                 }
@@ -646,16 +581,12 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_encrypt_split(EncArgs a) {
             u32x4 up = valid ? ld16(a.iv + 16ull * p) : z;      // the unit before the quad (IV first)
             uint32_t w[16];
             for (uint32_t q = 0; q <= wq; ++q) {
-                SPLIT_PROBE(const uint64_t pw = clock64(); bool pwt = false;)
-                while (__hip_atomic_load(produced, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < count + 1u) {
-                    SPLIT_PROBE(pwt = true;)
+                while (__hip_atomic_load(produced, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < count + 1u)
                     __builtin_amdgcn_s_sleep(1);
-                }
-                SPLIT_PROBE(if (pwt) { pr_wait += clock64() - pw; ++pr_n; })
                 const uint32_t nst = q < nq ? 4u : tb;
                 const bool act = valid && q <= nq;
                 u32x4 c[4];
-                if (!RB && lane) {
+                if (!ILV && lane) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) c[j] = mine[64 * j];
                 } else {
@@ -665,7 +596,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_encrypt_split(EncArgs a) {
                 ++count;
                 // the slot's reads (every lane's) complete before the AES wave
                 // may overwrite it
-                if (!RB) {
+                if (!ILV) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     if (lane == 0u)
                         __hip_atomic_store(consumed, count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -698,15 +629,6 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_encrypt_split(EncArgs a) {
             }
         }
     }
-#ifdef RNSTOK_SPLIT_PROBE
-    if (lane == 0u) {
-        const uint32_t r = aes ? 0u : 1u;
-        atomicAdd(&g_split_probe[r], pr_wait);
-        atomicAdd(&g_split_probe[2 + r], pr_n);
-        atomicAdd(&g_split_probe[4 + r], clock64() - pr_t0);
-        atomicAdd(&g_split_probe[6 + r], 1ull);
-    }
-#endif
     clk.finish(a.clk);
 }
 
@@ -890,12 +812,6 @@ constexpr uint32_t L4_SLOTS = 2u;
 // only meet the barriers.  In a launch of a few tokens (one Token call) their
 // chains on garbage took issue slots from the live AES and hashing chains
 // that share their SIMDs.
-#ifndef RNSTOK_L4_SKIP_IDLE
-#define RNSTOK_L4_SKIP_IDLE 1
-#endif
-#ifndef RNSTOK_L4_HASH_FIRST
-#define RNSTOK_L4_HASH_FIRST 1
-#endif
 constexpr uint32_t LDS_ENC_LONG4_BYTES = L4_RING + L4_SLOTS * L4_TOK * 64u;   // + 2 slots x 128 tokens x 64 B
 
 // DPP quad_perm: lane j of each group of four reads lane (j + K) & 3.
@@ -960,13 +876,13 @@ __global__ __launch_bounds__(L4_THREADS) void k_encrypt_long4(EncArgs a) {
     clk.start(a.clk);
     const Lanes LN(threadIdx.x & 31u);
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    // RNSTOK_L4_HASH_FIRST: in a launch of at most 64 tokens the hashing
+    // Hashing waves first: in a launch of at most 64 tokens the hashing
     // waves are waves 0-1 and the first tokens' AES wave is wave 2, so its
     // AES and hashing chains run on different SIMDs (else waves 0 and 8 shared
     // SIMD 0): one 383-B token -2 %.  Full workgroups keep the AES waves
     // first: hashing first there cost the c4 rank share's encrypt 2.24 ->
     // 3.39 M cycles (profiles/r06_latency_kernels/c4_share_hash_first.txt).
-    const bool hf = RNSTOK_L4_HASH_FIRST && a.n <= L4_HASH_TOK;                 // launch-uniform
+    const bool hf = a.n <= L4_HASH_TOK;                                         // launch-uniform
     const uint32_t hw = hf ? (wave < L4_HASH_WAVES ? L4_AES_WAVES + wave : wave - L4_HASH_WAVES) : wave;
     const bool aes = hw < L4_AES_WAVES;
     const uint32_t col = threadIdx.x & 3u;
@@ -983,7 +899,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_encrypt_long4(EncArgs a) {
         const uint32_t p = valid ? (a.order ? a.order[t] : t) : 0u;
         const uint8_t *P = a.pt + (valid ? in_off(a.pt_off, a.pt_stride, p) : 0);
         uint8_t *O = a.tok + (valid ? in_off(a.tok_off, a.tok_stride, p) : 0);
-        const bool live = !RNSTOK_L4_SKIP_IDLE || __ballot(valid) != 0ull;     // wave-uniform
+        const bool live = __ballot(valid) != 0ull;                             // wave-uniform
         // this lane's column of the plaintext blocks of quad k (the tail quad: tb blocks, the last padded)
         auto load_quad = [&](uint32_t k, uint32_t x[4]) {
 #pragma unroll
@@ -1016,11 +932,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_encrypt_long4(EncArgs a) {
                 if (live) {
 #pragma unroll
                     for (int b = 0; b < 4; ++b) {
-#ifndef RNSTOK_L4_PROBE_SHA_ONLY        // timing probe: no AES (wrong tokens)
                         cq[b] = enc_block4<NR>(x[b] ^ prev, rk, LN);
-#else
-                        cq[b] = x[b] ^ prev;
-#endif
                         prev = cq[b];
                     }
                 }
@@ -1048,13 +960,11 @@ __global__ __launch_bounds__(L4_THREADS) void k_encrypt_long4(EncArgs a) {
                 lds_q *r = (lds_q *)(uintptr_t)(L4_RING + ((q % L4_SLOTS) * L4_TOK + slot) * 64u);
                 const u32x4 c0 = r[0], c1 = r[1], c2 = r[2], c3 = r[3];
                 if (q < nq) {
-#ifndef RNSTOK_L4_PROBE_AES_ONLY        // timing probe: no HMAC (wrong tags)
                     if (live) {
                         uint32_t w[16];
                         sha_units(w, prev, c0, c1, c2);
                         sha256_compress(h, w);
                     }
-#endif
                     prev = c3;
                 } else if (valid) {
                     // tail quad: units prev, c0..c_{tb-1} (+ final padding), then the outer hash
@@ -1088,7 +998,7 @@ __global__ __launch_bounds__(L4_THREADS) void k_encrypt_long4(EncArgs a) {
 // VGPRs, 4 waves/SIMD) when one pass covers the batch (e.g. 16 KiB Resource
 // tokens, one per lane: 512 x 2 passes at 768 was 9 % slower).
 template <int NR, bool PERKEY, int WG = PERKEY ? WG_PERKEY_DEC : WG_DEC, bool ILV = false>
-__global__ RT_OCC __launch_bounds__(WG) void k_decrypt(DecArgs a) {
+__global__ __launch_bounds__(WG) void k_decrypt(DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tab_u32[];
     LaunchClock clk;
     clk.start(a.clk);
@@ -1150,9 +1060,9 @@ __global__ RT_OCC __launch_bounds__(WG) void k_decrypt(DecArgs a) {
             // through one sha256_compress.
             const u32x4 z = {0u, 0u, 0u, 0u};
             u32x4 prev = ld16(Kt);
-            // (RNSTOK_DEC_TAG_EARLY: the tag's two units loaded before the quad
-            // loop, so the compare after it does not wait on them)
-            constexpr bool TAG_EARLY = RNSTOK_DEC_TAG_EARLY && !PERKEY && WG <= 768;
+            // (the tag's two units are loaded before the quad loop, so the
+            // compare after it does not wait on them)
+            constexpr bool TAG_EARLY = !PERKEY && WG <= 768;
             u32x4 tag0, tag1;
             if (TAG_EARLY) {
                 tag0 = ld16(Kt + US * ((T >> 4) - 2u));
@@ -1165,8 +1075,9 @@ __global__ RT_OCC __launch_bounds__(WG) void k_decrypt(DecArgs a) {
             // packed rows: an even quad loads the next quad's 64 B with its
             // own, so the 128-B line the two share is read while it is in
             // L2 (one quad apart, an XCD's waves have streamed more than its
-            // L2 through and the line is fetched again: 2.7x read traffic)
-            constexpr bool PAIR = RNSTOK_DEC_PAIR && !ILV && !PERKEY && WG <= 768;   // (1024: 11 -> 38 VGPRs spilled)
+            // L2 through and the line is fetched again: 2.7x read traffic);
+            // fetch -21 %, time -1.6 %
+            constexpr bool PAIR = !ILV && !PERKEY && WG <= 768;   // (1024: 11 -> 38 VGPRs spilled)
             u32x4 nx[4];
 #pragma nounroll
             for (uint32_t q = 0; q <= nq; ++q) {
@@ -1266,10 +1177,7 @@ __global__ RT_OCC __launch_bounds__(WG) void k_decrypt(DecArgs a) {
 // chain, so the AES waves never wait on it.  The LDS image makes room for the
 // 64 KiB ring: T0/T1 only (Td2 = rotl16(Td0), Td3 = rotl16(Td1), one
 // v_alignbit per column on the XOR of the two lookups) and a 16-replica InvS.
-#ifndef RNSTOK_DL2_AES_WAVES
-#define RNSTOK_DL2_AES_WAVES 12
-#endif
-constexpr uint32_t DL2_TOK = 128, DL2_AES_WAVES = RNSTOK_DL2_AES_WAVES, DL2_THREADS = 64u * (4u + DL2_AES_WAVES);
+constexpr uint32_t DL2_TOK = 128, DL2_AES_WAVES = 12, DL2_THREADS = 64u * (4u + DL2_AES_WAVES);
 constexpr uint32_t DL2_INVS = 0x10000;                       // 256 rows x 64 B: InvS[x]*0x01010101 x16
 constexpr uint32_t DL2_RING = 0x14000;                       // 2 slots x 16 quads x 128 tokens x 16 B
 constexpr uint32_t DL2_SLOT = 16u * DL2_TOK * 16u;           // 32 KiB
@@ -1279,14 +1187,6 @@ constexpr uint32_t LDS_DL2_BYTES = DL2_PADN + 4u * DL2_TOK;
 // The producers also schedule the final padded block, so the chain runs it
 // from the ring like the others (its own schedule inline took a third more
 // instructions per round).
-#ifndef RNSTOK_DL2_FINAL
-#define RNSTOK_DL2_FINAL 1
-#endif
-constexpr bool DL2_FINAL = RNSTOK_DL2_FINAL;
-#ifndef RNSTOK_DL2_SKIP_IDLE
-#define RNSTOK_DL2_SKIP_IDLE 1
-#endif
-constexpr bool DL2_SKIP_IDLE = RNSTOK_DL2_SKIP_IDLE;
 
 __device__ void fill_tables_dl2(uint32_t *tab, const uint8_t *inv) {
     const uint32_t lane = threadIdx.x & 31u;
@@ -1383,20 +1283,7 @@ __global__ __launch_bounds__(DL2_THREADS) void k_decrypt_long2(DecArgs a) {
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     const uint32_t T = a.uni_len, nb = (T - 48u) >> 4, nquads = (nb + 3u) >> 2, tbl = nb - 4u * (nquads - 1u);
     const uint32_t M = T - 32u, full = M >> 6;                 // full = 0 for a 64-B token: no chain steps
-#if defined(RNSTOK_DL2_PROBE_AES_ONLY)          // timing probes (wrong statuses): one side of the kernel only
-    const bool consumer = false, producer = false;
-    if (wave < 4u) {
-        __syncthreads();
-        __syncthreads();
-        for (uint32_t base = blockIdx.x * DL2_TOK + gridDim.x * DL2_TOK; base < a.n; base += gridDim.x * DL2_TOK) {
-            __syncthreads();
-            __syncthreads();
-        }
-        return;
-    }
-#else
     const bool consumer = wave < 2u, producer = wave == 2u || wave == 3u;
-#endif
     const uint32_t pair = wave & 1u;                            // consumer p <-> producer p: tokens 64p..64p+63
     const uint32_t ready_f = DL2_FLAGS + 4u * pair, done_f = DL2_FLAGS + 8u + 4u * pair;
     Keys<NR, false> K;
@@ -1406,18 +1293,18 @@ __global__ __launch_bounds__(DL2_THREADS) void k_decrypt_long2(DecArgs a) {
         const uint32_t ntok = a.n - base < DL2_TOK ? a.n - base : DL2_TOK;
         const uint32_t slot_tok = pair * 64u + lane;            // this lane's column of the ring
         uint32_t diff = 1;
-        // DL2_SKIP_IDLE: a batch of at most 64 tokens leaves chain pair 1
+        // A batch of at most 64 tokens leaves chain pair 1
         // without a token; it skips its chains, and only the AES waves on
         // SIMDs 1 and 3 take quads, so the live chain waves (0 on SIMD 0, 2 on
         // SIMD 2) share their SIMDs with nothing (one Token call)
-        const bool idle = DL2_SKIP_IDLE && ((consumer || producer) ? pair * 64u >= ntok : (ntok <= 64u && !(wave & 1u)));
+        const bool idle = (consumer || producer) ? pair * 64u >= ntok : (ntok <= 64u && !(wave & 1u));
         if (idle) {
         } else if (producer) {
             // tokens past the batch hash a copy of its last token (results unused)
             const uint32_t t = base + (slot_tok < ntok ? slot_tok : ntok - 1u);
             const uint8_t *Kt = a.tok + in_off(a.tok_off, a.tok_stride, a.order ? a.order[t] : t);
-            // the final padded block (the last fu units of iv || ct) too, with DL2_FINAL
-            const uint32_t fu = (M - 64u * full) >> 4, nblk = full + (DL2_FINAL ? 1u : 0u);
+            // the final padded block (the last fu units of iv || ct) too
+            const uint32_t fu = (M - 64u * full) >> 4, nblk = full + 1u;
             const u32x4 z = {0u, 0u, 0u, 0u};
             auto load_block = [&](uint32_t i, u32x4 &c0, u32x4 &c1, u32x4 &c2, u32x4 &c3) {
                 const uint8_t *B = Kt + 64ull * i;
@@ -1430,7 +1317,7 @@ __global__ __launch_bounds__(DL2_THREADS) void k_decrypt_long2(DecArgs a) {
             for (uint32_t i = 0; i < nblk; ++i) {
                 uint32_t w[16];
                 sha_units(w, b0, b1, b2, b3);
-                if (DL2_FINAL && i == full) {
+                if (i == full) {
                     uint32_t fin[16];
                     sha_final_block(fin, w, fu, (uint64_t)(64u + M) * 8u);
 #pragma unroll
@@ -1479,7 +1366,7 @@ __global__ __launch_bounds__(DL2_THREADS) void k_decrypt_long2(DecArgs a) {
             // the tag, requested before the chain (a Token call's token sits in
             // pinned host memory: one PCIe round trip less at the end)
             const u32x4 r0 = ld16(Kt + M), r1 = ld16(Kt + M + 16);
-            for (uint32_t i = 0; i < full + (DL2_FINAL ? 1u : 0u); ++i) {
+            for (uint32_t i = 0; i < full + 1u; ++i) {
                 dl2_wait(ready_f, i + 1u);
                 const lds_quad_t *ring = (const lds_quad_t *)(uintptr_t)(DL2_RING + (i & 1u) * DL2_SLOT) + slot_tok;
                 uint32_t v[8];
@@ -1504,13 +1391,6 @@ __global__ __launch_bounds__(DL2_THREADS) void k_decrypt_long2(DecArgs a) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) h[k] += v[k];
             }
-            if (!DL2_FINAL) {
-                const uint32_t fu = (M - 64u * full) >> 4;
-                const u32x4 z = {0u, 0u, 0u, 0u};
-                const uint8_t *R = Kt + 64ull * full;
-                sha_final_units(h, fu, fu > 0 ? ld16(R) : z, fu > 1 ? ld16(R + 16) : z, fu > 2 ? ld16(R + 32) : z,
-                                (uint64_t)(64u + M) * 8u);
-            }
             load_uniform8(opad, a.rec + REC_OPAD);
             uint32_t tag[8];
             hmac_outer(tag, h, opad);
@@ -1529,9 +1409,6 @@ __global__ __launch_bounds__(DL2_THREADS) void k_decrypt_long2(DecArgs a) {
                 uint32_t c0 = 0u;
                 if (lane == 0u) c0 = __hip_atomic_fetch_add(next, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 c0 = __builtin_amdgcn_readfirstlane(c0);
-#ifdef RNSTOK_DL2_PROBE_SHA_ONLY
-                break;
-#endif
                 if (c0 >= items) break;                 // wave-uniform
                 // the tail chunk's idle lanes skip the body but stay in the
                 // loop (a divergent `continue` let them re-enter the loop
@@ -1582,9 +1459,7 @@ __global__ __launch_bounds__(DL2_THREADS) void k_decrypt_long2(DecArgs a) {
         if (threadIdx.x < 16u) tab_u32[(DL2_FLAGS >> 2) + threadIdx.x] = 0u;     // counters restart per batch
         __syncthreads();
     }
-#ifndef RNSTOK_DL2_PROBE_AES_ONLY
     clk.finish(a.clk);
-#endif
 }
 
 // --------------------------------------------------------- ratchet trials --
@@ -1858,36 +1733,19 @@ static Shape shape_for(uint32_t n, int max_threads, int n_cu) {
     uint64_t g = ((uint64_t)n + t - 1) / t;
     if (g > (uint64_t)n_cu) g = n_cu;
     if (g < 1) g = 1;
-#ifndef RNSTOK_NO_SMALL_FILL
     // One workgroup (up to 64 packets, e.g. a single Token.encrypt): widen it
     // so the LDS table image is written by 512 threads, not 64 (the extra
     // waves find no packet and leave after fill_tables).
     if (g == 1 && t < 512 && max_threads >= 512) t = 512;
-#endif
     return {(int)g, (int)t};
 }
 
-#ifndef RNSTOK_SPLIT_ENC            // 0: every single-key uniform batch on k_encrypt (the A/B baseline)
-#define RNSTOK_SPLIT_ENC 1
-#endif
-#ifndef RNSTOK_SPLIT_ROWS_RB          // packed rows: LDS ring (0) or read-back (1)
-#define RNSTOK_SPLIT_ROWS_RB 0
-#endif
-#ifndef RNSTOK_SPLIT_ILV_RB           // interleaved: read-back (1) or LDS ring (0)
-#define RNSTOK_SPLIT_ILV_RB 1
-#endif
-// Split-role encrypt (k_encrypt_split): uniform lengths, at least one
-// 64-packet batch per AES wave of every CU.
-#ifndef RNSTOK_SPLIT_PERKEY          // per-packet keys (c3) on the split kernel too: 0.845 vs 0.912 ms rows,
-#define RNSTOK_SPLIT_PERKEY 1        // 0.770 vs 0.852 interleaved (profiles/r04_split/r04i_perkey_ab.txt)
-#endif
-#ifndef RNSTOK_SPLIT_GEN             // packed / length-ordered batches (c5) on the split kernel too
-#define RNSTOK_SPLIT_GEN 1
-#endif
-static bool use_split_enc(const EncArgs &a, int n_cu) {
-    const bool gen = a.pt_len || a.order || a.queue || a.pt_off;
-    return RNSTOK_SPLIT_ENC && (!a.key_idx || RNSTOK_SPLIT_PERKEY) && (!gen || RNSTOK_SPLIT_GEN) &&
-           (uint64_t)a.n >= 64ull * SPLIT_AES_WAVES * (uint64_t)n_cu;
+// Split-role encrypt (k_encrypt_split): at least one 64-packet batch per AES
+// wave of every CU.  Per-packet keys (c3) run on it too: 0.845 vs 0.912 ms
+// rows, 0.770 vs 0.852 interleaved (profiles/r04_split/r04i_perkey_ab.txt);
+// so do packed / length-ordered batches (c5).
+static bool use_split_enc(uint32_t n, int n_cu) {
+    return (uint64_t)n >= 64ull * SPLIT_AES_WAVES * (uint64_t)n_cu;
 }
 static uint64_t split_grid(uint32_t n, int n_cu) {
     const uint64_t batches = (n + 63ull) / 64ull;
@@ -1897,22 +1755,22 @@ static uint64_t split_grid(uint32_t n, int n_cu) {
 template <int NR>
 static hipError_t launch_enc_split_nr(const EncArgs &a, int n_cu, hipStream_t s) {
     const uint64_t grid = split_grid(a.n, n_cu);
-#define RT_SPLIT(ILV_, RB_, PK_, GEN_)                                                                        \
-    hipLaunchKernelGGL((k_encrypt_split<NR, ILV_, RB_, PK_, GEN_>), dim3((unsigned)grid), dim3(SPLIT_THREADS), \
+#define RT_SPLIT(ILV_, PK_, GEN_)                                                                        \
+    hipLaunchKernelGGL((k_encrypt_split<NR, ILV_, PK_, GEN_>), dim3((unsigned)grid), dim3(SPLIT_THREADS), \
                        LDS_ENC_SPLIT_BYTES, s, a)
     const bool gen = a.pt_len || a.order || a.queue || a.pt_off;
     if (gen && a.key_idx)
-        RT_SPLIT(false, false, true, true);
+        RT_SPLIT(false, true, true);
     else if (gen)
-        RT_SPLIT(false, false, false, true);
+        RT_SPLIT(false, false, true);
     else if (a.ilv && a.key_idx)
-        RT_SPLIT(true, RNSTOK_SPLIT_ILV_RB, true, false);
+        RT_SPLIT(true, true, false);
     else if (a.ilv)
-        RT_SPLIT(true, RNSTOK_SPLIT_ILV_RB, false, false);
+        RT_SPLIT(true, false, false);
     else if (a.key_idx)
-        RT_SPLIT(false, RNSTOK_SPLIT_ROWS_RB, true, false);
+        RT_SPLIT(false, true, false);
     else
-        RT_SPLIT(false, RNSTOK_SPLIT_ROWS_RB, false, false);
+        RT_SPLIT(false, false, false);
 #undef RT_SPLIT
     return hipGetLastError();
 }
@@ -1969,21 +1827,13 @@ static hipError_t launch_enc_long_nr(const EncArgs &a, int n_cu, hipStream_t s) 
 // they take any length.  So does the per-key k_encrypt_long (2^15 x 500 B
 // with 64 keys: 101 -> 80 us; x 1000 B: 172 -> 129 us; even at 100 B;
 // profiles/r02x_lat_perkey.txt).
-#ifndef RNSTOK_LONG_MIN_LEN
-#define RNSTOK_LONG_MIN_LEN 0u
-#endif
-#ifndef RNSTOK_LONG_PERKEY_MIN_LEN
-#define RNSTOK_LONG_PERKEY_MIN_LEN 0u
-#endif
 // Tokens per CU up to which the long-token kernels run (one persistent
-// workgroup of 128 chains per CU).  A build with a larger value forces them
-// onto big batches: the measured comparison of their lane-cooperative CBC
-// and wave-split HMAC with one packet per lane at c2.
-#ifndef RNSTOK_LONG_MAX_PER_CU
-#define RNSTOK_LONG_MAX_PER_CU 128ull
-#endif
-static bool use_long(uint32_t n, const uint32_t *len, uint32_t uni, int n_cu, uint32_t min_len) {
-    return len == nullptr && uni >= min_len && (uint64_t)n <= RNSTOK_LONG_MAX_PER_CU * (uint64_t)n_cu;
+// workgroup of 128 chains per CU).  A larger value forces them onto big
+// batches: the measured comparison of their lane-cooperative CBC and
+// wave-split HMAC with one packet per lane at c2.
+constexpr uint64_t LONG_MAX_PER_CU = 128;
+static bool use_long(uint32_t n, bool packed, int n_cu) {
+    return !packed && (uint64_t)n <= LONG_MAX_PER_CU * (uint64_t)n_cu;
 }
 
 template <int NR>
@@ -2012,14 +1862,8 @@ static hipError_t balance(Args &a, Shape sh, SpareQueue *spare, hipStream_t s, b
 }
 
 int plan_encrypt(uint32_t n, bool packed, uint32_t uni_len, bool per_key, int n_cu) {
-    const uint32_t *len = packed ? &uni_len : nullptr;   // any non-null marks a packed batch
-#ifndef RNSTOK_NO_LONG4
-    if (!per_key && use_long(n, len, uni_len, n_cu, RNSTOK_LONG_MIN_LEN)) return RT_KERNEL_ENC_LONG4;
-#endif
-    if (use_long(n, len, uni_len, n_cu, RNSTOK_LONG_PERKEY_MIN_LEN)) return RT_KERNEL_ENC_LONG;
-    EncArgs a{};
-    a.n = n; a.uni_len = uni_len; a.pt_len = len; a.key_idx = per_key ? &uni_len : nullptr;
-    if (use_split_enc(a, n_cu)) return RT_KERNEL_ENC_SPLIT;
+    if (use_long(n, packed, n_cu)) return per_key ? RT_KERNEL_ENC_LONG : RT_KERNEL_ENC_LONG4;
+    if (use_split_enc(n, n_cu)) return RT_KERNEL_ENC_SPLIT;
     return RT_KERNEL_GENERAL;
 }
 
@@ -2031,7 +1875,7 @@ hipError_t launch_encrypt(const EncArgs &args, int nr, int n_cu, SpareQueue *spa
     if (plan == RT_KERNEL_ENC_LONG)
         return nr == 14 ? launch_enc_long_nr<14>(a, n_cu, s) : launch_enc_long_nr<10>(a, n_cu, s);
 
-    if (use_split_enc(a, n_cu)) {
+    if (use_split_enc(a.n, n_cu)) {
         // Uniform row batches that do not give every AES wave the same number
         // of 64-packet batches take them from a chunk counter instead of the
         // static stride, as k_decrypt's ragged batches do (balance): 2^20 x
@@ -2039,12 +1883,13 @@ hipError_t launch_encrypt(const EncArgs &args, int nr, int n_cu, SpareQueue *spa
         // wave) -4.8..-5.8 %, 1.5 M x 500 B -4.6..-10 % on three boxes
         // (profiles/r05h_dyn/).  Short packets keep the stride: a counter
         // fetch is an L2 round trip per batch, +18 % at 100 B.
+        constexpr uint32_t SPLIT_DYN_MIN_LEN = 256;
         const bool gen = a.pt_len || a.order || a.queue || a.pt_off;
         const uint64_t waves = split_grid(a.n, n_cu) * SPLIT_AES_WAVES, batches = (a.n + 63ull) / 64ull;
         bool took = false;
         uint32_t slot = 0;
-        if (RNSTOK_SPLIT_DYN && !gen && !a.ilv && spare && a.n <= QUEUE_MAX_N && batches % waves != 0 &&
-            a.uni_len >= RNSTOK_SPLIT_DYN_MIN_LEN) {
+        if (!gen && !a.ilv && spare && a.n <= QUEUE_MAX_N && batches % waves != 0 &&
+            a.uni_len >= SPLIT_DYN_MIN_LEN) {
             a.queue = spare->acquire(s, &slot);
             took = a.queue != nullptr;
             if (took) {
@@ -2078,8 +1923,7 @@ static hipError_t launch_dec_long_nr(const DecArgs &a, int n_cu, hipStream_t s) 
 int plan_decrypt(uint32_t n, bool packed, uint32_t uni_len, bool per_key, int n_cu) {
     // long mode: one key, uniform well-formed tokens (whole blocks, at least
     // one), few per CU
-    if (!per_key && !packed && uni_len >= 64u && uni_len >= 48u + RNSTOK_LONG_MIN_LEN &&
-        ((uni_len - 48u) & 15u) == 0 && (uint64_t)n <= RNSTOK_LONG_MAX_PER_CU * (uint64_t)n_cu)
+    if (!per_key && uni_len >= 64u && ((uni_len - 48u) & 15u) == 0 && use_long(n, packed, n_cu))
         return RT_KERNEL_DEC_LONG2;
     return RT_KERNEL_GENERAL;
 }
@@ -2094,7 +1938,8 @@ hipError_t launch_decrypt(const DecArgs &args, int nr, int n_cu, SpareQueue *spa
     // 2^20 tokens of 16-250 B plaintext -8..-31 %, 350-430 B +1..+2 %,
     // profiles/r05r_short/)
     const uint64_t per_cu = ((uint64_t)a.n + n_cu - 1) / n_cu;
-    const bool short_tok = !a.tok_len && a.uni_len <= RNSTOK_DEC1024_MAX_TOKEN;
+    constexpr uint32_t DEC1024_MAX_TOKEN = 320;          // (plaintexts up to 271 B)
+    const bool short_tok = !a.tok_len && a.uni_len <= DEC1024_MAX_TOKEN;
     const int max_t = a.key_idx ? WG_PERKEY_DEC : ((per_cu <= 1024u || short_tok) ? 1024 : WG_DEC);
     const Shape sh = shape_for(a.n, max_t, n_cu);
     bool took = false;
@@ -2146,30 +1991,20 @@ hipError_t configure_kernels() {
     RT_CFG((k_decrypt<10, false, WG_DEC, true>), LDS_DEC_BYTES);
     RT_CFG((k_decrypt<10, false, 1024, true>), LDS_DEC_BYTES);
     RT_CFG((k_decrypt<10, true, WG_PERKEY_DEC, true>), LDS_DEC_BYTES);
-    RT_CFG((k_encrypt_split<14, false, false, false, true>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<14, false, false, true, true>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<10, false, false, false, true>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<10, false, false, true, true>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<14, false, RNSTOK_SPLIT_ROWS_RB, false>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<14, true, RNSTOK_SPLIT_ILV_RB, false>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<10, false, RNSTOK_SPLIT_ROWS_RB, false>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<10, true, RNSTOK_SPLIT_ILV_RB, false>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<14, false, RNSTOK_SPLIT_ROWS_RB, true>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<14, true, RNSTOK_SPLIT_ILV_RB, true>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<10, false, RNSTOK_SPLIT_ROWS_RB, true>), LDS_ENC_SPLIT_BYTES);
-    RT_CFG((k_encrypt_split<10, true, RNSTOK_SPLIT_ILV_RB, true>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<14, false, false, true>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<14, false, true, true>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<10, false, false, true>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<10, false, true, true>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<14, false, false>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<14, true, false>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<10, false, false>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<10, true, false>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<14, false, true>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<14, true, true>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<10, false, true>), LDS_ENC_SPLIT_BYTES);
+    RT_CFG((k_encrypt_split<10, true, true>), LDS_ENC_SPLIT_BYTES);
 #undef RT_CFG
     return e;
 }
 
 }  // namespace rnstok
-
-#ifdef RNSTOK_SPLIT_PROBE
-// probe builds only: read and clear k_encrypt_split's wait counters
-extern "C" int rt_split_probe_read(unsigned long long *out) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rnstok::g_split_probe), sizeof(unsigned long long) * 8) != hipSuccess)
-        return -1;
-    const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(rnstok::g_split_probe), z, sizeof(z)) == hipSuccess ? 0 : -1;
-}
-#endif

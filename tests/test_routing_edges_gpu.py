@@ -2,8 +2,8 @@
 
 * the split encrypt takes its 64-packet batches from a chunk counter when
   the static stride would load its AES waves unevenly (batches not a multiple
-  of 8 x CUs) and packets are at least RNSTOK_SPLIT_DYN_MIN_LEN (256) bytes;
-* uniform tokens of at most RNSTOK_DEC1024_MAX_TOKEN (320) bytes decrypt on
+  of 8 x CUs) and packets are at least SPLIT_DYN_MIN_LEN (256) bytes;
+* uniform tokens of at most DEC1024_MAX_TOKEN (320) bytes decrypt on
   the 1024-thread instance at every batch size.
 
 Batch sizes and lengths just below, at and above each threshold, one key and

@@ -3,8 +3,9 @@
 unit-interleaved layout ... A/B it in one process").
 
   tools/build_variant.sh base
+  git apply tools/archive/knobs/split_tile.patch
   tools/build_variant.sh tile -DRNSTOK_SPLIT_TILE=1
-  python tools/c5_tile_ab.py build_exp/base/librnstok.so build_exp/tile/librnstok.so
+  python tools/archive/knobs/c5_tile_ab.py build_exp/base/librnstok.so build_exp/tile/librnstok.so
 
 One rank's c5 encrypt half: 2^19 packets of 64-4096 B, 65 536 keys, ordered
 longest first (as RT_F_SORT_BY_LENGTH orders them), on the split kernel's
@@ -22,7 +23,7 @@ import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
 sys.path.insert(0, ROOT)
 
 

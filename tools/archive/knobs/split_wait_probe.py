@@ -1,7 +1,9 @@
-"""Where k_encrypt_split's waves wait (probe build: -DRNSTOK_SPLIT_PROBE).
+"""Where k_encrypt_split's waves wait (probe build: split_wait_probe.patch
+beside this file, with -DRNSTOK_SPLIT_PROBE).
 
+  git apply tools/archive/knobs/split_wait_probe.patch
   tools/build_variant.sh splitprobe -DRNSTOK_SPLIT_PROBE
-  RNSTOK_LIB=build_exp/splitprobe/librnstok.so python tools/split_wait_probe.py [--length L] [--ilv]
+  RNSTOK_LIB=build_exp/splitprobe/librnstok.so python tools/archive/knobs/split_wait_probe.py [--length L] [--ilv]
 
 Per role (AES waves / hashing waves): the share of each wave's cycles (table
 fill to exit) spent polling the other role's counter, and how many quads
@@ -14,7 +16,7 @@ import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
 sys.path.insert(0, ROOT)
 
 

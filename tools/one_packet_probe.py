@@ -2,8 +2,10 @@
 plaintext length, k_encrypt_long4 / k_decrypt_long2 launched one at a time
 (synchronised after each, as a Token call is), with their own cycles, clock
 and workgroup span from the launch clock (rt_clock_stamps).  With a probe
-build (RNSTOK_L4_PROBE_AES_ONLY / _SHA_ONLY, RNSTOK_DL2_PROBE_*) it times
-one side of the kernel alone (the tokens are then wrong; nothing is checked).
+build (tools/archive/knobs/one_side_probes.patch applied, then
+-DRNSTOK_L4_PROBE_AES_ONLY / _SHA_ONLY or -DRNSTOK_DL2_PROBE_AES_ONLY /
+_SHA_ONLY) it times one side of the kernel alone (the tokens are then wrong;
+nothing is checked).
 
   RNSTOK_LIB=... python tools/one_packet_probe.py [--calls 300] [--lengths 100,383,1000]
 """
