@@ -18,7 +18,9 @@
  *   rt_map_hashes /    Resource hashmap          RNS/Resource.py:426-468 (map hashes + the
  *   rt_resource_hashmap_host                      collision guard), get_map_hash :505-506,
  *                                                receive_part :865-866
- *   rt_hdlc_frame      HDLC.escape + framing     RNS/Interfaces/TCPInterface.py:44-53, :323
+ *   rt_resource_hashes /  Resource hash + proof  RNS/Resource.py:436-439 (hash, expected_proof),
+ *   rt_resource_hashes_host                       :698-699 (receiver's check), :759-760 (prove)
+ *   rt_hdlc_frame     HDLC.escape + framing     RNS/Interfaces/TCPInterface.py:44-53, :323
  *   rt_hdlc_deframe    HDLC read loop            RNS/Interfaces/TCPInterface.py:387-410, :336-339
  *   rt_hdlc_deframe_slots  the same, each frame in a 128-B-aligned slot
  *   rt_ifac_mask       IFAC on transmit          RNS/Transport.py:1069-1101
@@ -72,7 +74,7 @@
 extern "C" {
 #endif
 
-#define RNSTOK_ABI_VERSION 2   /* 2: rt_hdlc_deframe_slots, rt_clock_stamps */
+#define RNSTOK_ABI_VERSION 3   /* 2: rt_hdlc_deframe_slots, rt_clock_stamps; 3: rt_resource_hashes* */
 
 /* Return codes (< 0: API misuse or runtime failure). */
 #define RT_OK        0
@@ -287,6 +289,31 @@ int rt_map_hashes(rt_ctx *ctx, const uint8_t *data, const uint64_t *part_off, co
 int rt_resource_hashmap_host(rt_ctx *ctx, const uint8_t *data, uint64_t size, uint32_t sdu,
                              const uint8_t *random_hash, uint32_t rh_len, uint32_t guard, uint8_t *hashmap,
                              uint32_t *first_collision);
+
+/* ---- Resource integrity hash and proof (RNS/Resource.py:436-439, 698-699, 759-760) */
+/* For n segments, DEVICE pointers, enqueued on the stream: segment i is
+ * data + seg_off[i] (seg_len[i] bytes, any alignment, 0 allowed) and
+ *   hash[i]  = SHA-256(segment_i || random_hashes[i*rh_len .. +rh_len))   (32 bytes)
+ *   proof[i] = SHA-256(segment_i || hash[i])                              (32 bytes)
+ * in one pass over the segment (rh_len <= 32; RANDOM_HASH_SIZE = 4 in the
+ * reference).  Sender: expect_hash NULL; hash[i][:16] is the truncated_hash
+ * and proof[i] the expected_proof.  Receiver: expect_hash (n x 32) holds the
+ * advertised hashes; status[i] = 0 when the computed hash equals it, else 1
+ * (Resource.CORRUPT), and proof[i] is computed over expect_hash[i]: the second
+ * half of the proof packet hash || proof for an intact segment, 32 zero bytes
+ * for a corrupt one (the reference never proves a corrupt resource).  proof
+ * may be NULL; status may be NULL unless expect_hash is given. */
+int rt_resource_hashes(rt_ctx *ctx, const uint8_t *data, const uint64_t *seg_off, const uint32_t *seg_len,
+                       const uint8_t *random_hashes, uint32_t rh_len, const uint8_t *expect_hash, uint8_t *hash,
+                       uint8_t *proof, int32_t *status, uint32_t n, void *stream);
+/* One segment in HOST memory; returns when hash (32 bytes), proof (32 bytes,
+ * may be NULL) and *status (may be NULL without expect_hash) are written. */
+int rt_resource_hashes_host(rt_ctx *ctx, const uint8_t *data, uint64_t size, const uint8_t *random_hash,
+                            uint32_t rh_len, const uint8_t *expect_hash, uint8_t *hash, uint8_t *proof,
+                            int32_t *status);
+/* Batches of fewer segments than this run one workgroup per segment
+ * (k_resource_hashes_split) instead of one lane per segment; same results. */
+uint32_t rt_resource_hash_split_below(void);
 
 /* ---- wire-side neighbours (framing, IFAC, packet header) --------------- */
 /* HDLC framing of n packets into one stream, in order: frame i is

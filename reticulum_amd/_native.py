@@ -19,7 +19,7 @@ RT_KERNEL_GENERAL, RT_KERNEL_ENC_LONG4, RT_KERNEL_ENC_LONG, RT_KERNEL_DEC_LONG2 
 RT_KERNEL_ENC_SPLIT = 4
 # the RNSTOK_ABI_VERSION (include/rnstok.h) these bindings are written for;
 # load() refuses any other build of the library
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 # (name, restype, argtypes) for every entry point declared in include/rnstok.h
 _vp, _u32, _u64, _i32, _int = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int
@@ -56,6 +56,9 @@ SIGNATURES = [
     ("rt_verify_trials_host", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     ("rt_map_hashes", _int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp]),
     ("rt_resource_hashmap_host", _int, [_vp, _vp, _u64, _u32, _vp, _u32, _u32, _vp, _vp]),
+    ("rt_resource_hashes", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
+    ("rt_resource_hashes_host", _int, [_vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
+    ("rt_resource_hash_split_below", _u32, []),
     ("rt_hdlc_frame_workspace_bytes", _u64, [_u32]),
     ("rt_hdlc_frame", _int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("rt_hdlc_deframe_workspace_bytes", _u64, [_u64]),

@@ -1040,6 +1040,63 @@ int rt_resource_hashmap_host(rt_ctx *c, const uint8_t *data, uint64_t size, uint
     return RT_OK;
 }
 
+// ------------------------------------------- Resource hash and proof --
+
+uint32_t rt_resource_hash_split_below(void) { return resource_hash_split_below(); }
+
+int rt_resource_hashes(rt_ctx *c, const uint8_t *data, const uint64_t *seg_off, const uint32_t *seg_len,
+                       const uint8_t *random_hashes, uint32_t rh_len, const uint8_t *expect_hash, uint8_t *hash,
+                       uint8_t *proof, int32_t *status, uint32_t n, void *stream) {
+    if (!c) return fail(RT_E_INVAL, "null context");
+    if (n == 0) return RT_OK;
+    if (!data || !seg_off || !seg_len || !hash)
+        return fail(RT_E_INVAL, "rt_resource_hashes: null data, segments or output");
+    if (rh_len > 32) return fail(RT_E_INVAL, "rt_resource_hashes: rh_len must be <= 32");
+    if (rh_len && !random_hashes) return fail(RT_E_INVAL, "rt_resource_hashes: null random_hashes");
+    if (expect_hash && !status) return fail(RT_E_INVAL, "rt_resource_hashes: expect_hash needs status");
+    ResHashArgs a{data, seg_off, seg_len, random_hashes, rh_len, expect_hash, hash, proof, status, n};
+    RT_HIP(hipSetDevice(c->device), "hipSetDevice");
+    RT_HIP(launch_resource_hashes(a, pick(c, stream)), "resource hash launch");
+    return RT_OK;
+}
+
+int rt_resource_hashes_host(rt_ctx *c, const uint8_t *data, uint64_t size, const uint8_t *random_hash,
+                            uint32_t rh_len, const uint8_t *expect_hash, uint8_t *hash, uint8_t *proof,
+                            int32_t *status) {
+    if (!c) return fail(RT_E_INVAL, "null context");
+    if (size > 0xffffffffull) return fail(RT_E_INVAL, "rt_resource_hashes_host: segment too large");
+    if ((size && !data) || !hash || (rh_len && !random_hash))
+        return fail(RT_E_INVAL, "rt_resource_hashes_host: null buffer");
+    if (rh_len > 32) return fail(RT_E_INVAL, "rt_resource_hashes_host: rh_len must be <= 32");
+    if (expect_hash && !status) return fail(RT_E_INVAL, "rt_resource_hashes_host: expect_hash needs status");
+    // workspace: data | random_hash | expect_hash | seg_off, seg_len | hash, proof, status
+    const uint64_t o_data = 0, o_rh = align16(size), o_exp = o_rh + 32, o_seg = o_exp + 32, o_out = o_seg + 16,
+                   total = o_out + 80;
+    StageLock L(c);
+    Stager &g = *L.g;
+    RT_HIP(hipSetDevice(c->device), "hipSetDevice");
+    int rc = ensure_work(g, total);
+    if (rc) return rc;
+    uint8_t *w = g.d_work;
+    hipStream_t s = g.stream;
+    struct { uint64_t off; uint32_t len, pad; } seg = {o_data, (uint32_t)size, 0u};
+    if (size) RT_HIP(hipMemcpyAsync(w + o_data, data, size, hipMemcpyHostToDevice, s), "H2D data");
+    if (rh_len) RT_HIP(hipMemcpyAsync(w + o_rh, random_hash, rh_len, hipMemcpyHostToDevice, s), "H2D random_hash");
+    if (expect_hash) RT_HIP(hipMemcpyAsync(w + o_exp, expect_hash, 32, hipMemcpyHostToDevice, s), "H2D expect_hash");
+    RT_HIP(hipMemcpyAsync(w + o_seg, &seg, 16, hipMemcpyHostToDevice, s), "H2D segment");
+    ResHashArgs a{w, (const uint64_t *)(w + o_seg), (const uint32_t *)(w + o_seg + 8), w + o_rh, rh_len,
+                  expect_hash ? w + o_exp : nullptr, w + o_out, proof ? w + o_out + 32 : nullptr,
+                  (int32_t *)(w + o_out + 64), 1u};
+    RT_HIP(launch_resource_hashes(a, s), "resource hash launch");
+    uint8_t back[80];
+    RT_HIP(hipMemcpyAsync(back, w + o_out, 80, hipMemcpyDeviceToHost, s), "D2H digests");
+    RT_HIP(hipStreamSynchronize(s), "stream sync");
+    memcpy(hash, back, 32);
+    if (proof) memcpy(proof, back + 32, 32);
+    if (status) memcpy(status, back + 64, 4);
+    return RT_OK;
+}
+
 // ------------------------------------------------------------------ HKDF --
 
 static int hkdf_check(rt_ctx *c, const uint8_t *ikm, uint32_t ikm_len, const uint8_t *context, uint32_t context_len,

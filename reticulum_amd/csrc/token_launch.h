@@ -98,6 +98,34 @@ struct MapArgs {
     uint32_t n_parts;
 };
 
+// Resource integrity hash and proof (resource_kernels.hip): segment i =
+// data + seg_off[i] (seg_len[i] bytes, any alignment, 0 allowed);
+// hash[i] = SHA-256(segment || random_hashes[i]), proof[i] = SHA-256(segment
+// || hash[i]).  With expect_hash (receiver) status[i] = 0 / 1 (hash differs:
+// Resource.CORRUPT), the proof is over expect_hash[i] and zero where status is 1.
+struct ResHashArgs {
+    const uint8_t *data;
+    const uint64_t *seg_off;
+    const uint32_t *seg_len;
+    const uint8_t *random_hashes;  // n x rh_len
+    uint32_t rh_len;               // <= 32
+    const uint8_t *expect_hash;    // n x 32 or null
+    uint8_t *hash;                 // n x 32
+    uint8_t *proof;                // n x 32 or null
+    int32_t *status;               // n or null
+    uint32_t n;
+};
+// Batches of fewer segments than this take k_resource_hashes_split (one
+// workgroup per segment); measured, DESIGN.md 4.4.  A variant build may
+// override it to time one kernel alone (tools/bench_resource_hash.py).
+#ifndef RNSTOK_RESOURCE_SPLIT_BELOW
+#define RNSTOK_RESOURCE_SPLIT_BELOW 1025u
+#endif
+constexpr uint32_t RES_HASH_SPLIT_BELOW = RNSTOK_RESOURCE_SPLIT_BELOW;
+constexpr uint32_t RES_HASH_THREADS = 64;
+uint32_t resource_hash_split_below();
+hipError_t launch_resource_hashes(const ResHashArgs &a, hipStream_t s);
+
 // Wire-side neighbours (wire_kernels.hip).
 struct IfacArgs {
     const uint8_t *pkt;

@@ -367,6 +367,36 @@ def map_hashes(data, out, salts, part_off=None, part_len=None, part_res=None, sd
                                     _p(first_collision), n_parts, _stream(stream, data.device)))
 
 
+def resource_hashes(data, seg_off, seg_len, random_hashes, hash_out, proof_out=None, expect_hash=None, status=None,
+                    stream=None):
+    """Resource integrity hash and proof over device buffers (Resource.py:
+    436-439, 698-699, 759-760), one pass per segment: segment i is
+    data[seg_off[i] : seg_off[i] + seg_len[i]] (seg_off (n,) int64, seg_len
+    (n,) int32, any alignment, 0 allowed); hash_out (n, 32) uint8 receives
+    SHA-256(segment || random_hashes[i]) and proof_out (n, 32) SHA-256(segment
+    || hash).  random_hashes is (n, R) uint8 with R <= 32.  With expect_hash
+    (n, 32) (receiver) status (n,) int32 receives 0 where the hash matches and
+    1 where it does not (CORRUPT), the proof is taken over expect_hash and is
+    32 zero bytes for a corrupt segment."""
+    _check_u8(data, random_hashes, hash_out, proof_out, expect_hash)
+    n = seg_off.numel()
+    if seg_off.dtype != torch.int64:
+        raise ValueError("seg_off must be int64")
+    _check_i32(n, seg_len=seg_len, status=status)
+    if random_hashes.dim() != 2 or random_hashes.shape[0] != n or random_hashes.shape[1] > 32:
+        raise ValueError("random_hashes must be (n, R) with R <= 32")
+    for name, t in (("hash_out", hash_out), ("proof_out", proof_out), ("expect_hash", expect_hash)):
+        if t is not None and t.numel() != 32 * n:
+            raise ValueError(f"{name} must hold n x 32 bytes")
+    if expect_hash is not None and status is None:
+        raise ValueError("expect_hash needs a status tensor")
+    lib = _native.load()
+    rh_len = random_hashes.shape[1]
+    _native.check(lib.rt_resource_hashes(_native.context(data.device.index), _p(data), _p(seg_off), _p(seg_len),
+                                         _p(random_hashes) if rh_len else None, rh_len, _p(expect_hash), _p(hash_out),
+                                         _p(proof_out), _p(status), n, _stream(stream, data.device)))
+
+
 # ---------------------------------------------------------------- wire side --
 # Device-resident forms of reticulum_amd.wire (wire_kernels.hip): flat uint8
 # buffers, int64 offsets, int32 lengths, enqueued on the stream, no sync.
