@@ -32,7 +32,9 @@
  *   rt_token_spans     packet.data (the token)   RNS/Packet.py:262-275 (data after the header)
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
- *   rt_verify_trials*  ratchet trial loop        Identity.py:865-878 (first ratchet whose key
+ *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
+ *   rt_keyset_create_x25519  the same keying from the exchange on: Identity.py:812-829, 861-871
+ *   rt_verify_trials*  ratchet trial loop       Identity.py:865-878 (first ratchet whose key
  *                                                opens the token; Token.py:77-84,114)
  *
  * Conventions
@@ -246,6 +248,40 @@ rt_keyset *rt_keyset_create_hkdf(rt_ctx *ctx, const uint8_t *ikm, uint64_t ikm_s
                                  const uint8_t *salt, uint64_t salt_stride, uint32_t salt_len,
                                  const uint8_t *context, uint32_t context_len, uint32_t key_len, uint32_t n,
                                  void *stream);
+
+/* ---- X25519 (RNS/Cryptography/X25519.py:49-93) -------------------------- */
+/* n independent exchanges, one per lane: out_i = X25519(scalar_i, point_i),
+ * 32 bytes each, by the RFC 7748 ladder.  scalar_i at scalars + i*scalar_stride
+ * (stride 0: one scalar for all, the receiver's case); point_i at
+ * points + point_off[i] when point_off != NULL (e.g. the ephemeral public key
+ * at the head of each token, read in place), else points + i*point_stride
+ * (stride 0: one point for all, the sender's target key); points == NULL: the
+ * base point 9 (public keys).  A non-zero stride is at least 32.  No alignment
+ * is assumed.  As the reference's internal provider: the scalar is clamped
+ * (_fix_secret), bit 255 of a point is ignored and a point >= p is taken
+ * mod p (_fix_base_point), and a low-order point gives 32 zero bytes without
+ * an error.  Constant time: no branch or address depends on a scalar.
+ * rt_x25519 takes DEVICE pointers and only enqueues; rt_x25519_host takes HOST
+ * pointers and returns when `out` is filled.  n == 0 is RT_OK. */
+int rt_x25519(rt_ctx *ctx, const uint8_t *scalars, uint64_t scalar_stride, const uint8_t *points,
+              uint64_t point_stride, const uint64_t *point_off, uint8_t *out, uint64_t out_stride,
+              uint32_t n, void *stream);
+int rt_x25519_host(rt_ctx *ctx, const uint8_t *scalars, uint64_t scalar_stride, const uint8_t *points,
+                   uint64_t point_stride, const uint64_t *point_off, uint8_t *out, uint64_t out_stride,
+                   uint32_t n);
+/* Identity.encrypt / decrypt keying in one call (Identity.py:812-829, 861-871,
+ * 887-888): the n shared secrets X25519(scalar_i, point_i) (arguments as
+ * rt_x25519, DEVICE pointers) go to a stream-ordered device temporary, the
+ * key derivation and key setup of rt_keyset_create_hkdf run over them
+ * (ikm_len 32; salt, context and key_len as there), and the temporary is
+ * freed in stream order: key i of the keyset is
+ * Token(hkdf(key_len, X25519(scalar_i, point_i), salt_i, context)), and
+ * neither the shared secrets nor the derived keys leave the device. */
+rt_keyset *rt_keyset_create_x25519(rt_ctx *ctx, const uint8_t *scalars, uint64_t scalar_stride,
+                                   const uint8_t *points, uint64_t point_stride, const uint64_t *point_off,
+                                   const uint8_t *salt, uint64_t salt_stride, uint32_t salt_len,
+                                   const uint8_t *context, uint32_t context_len, uint32_t key_len, uint32_t n,
+                                   void *stream);
 
 /* ---- ratchet trials (Identity.decrypt, RNS/Identity.py:865-878) --------- */
 /* Identity.decrypt tries the receiver's ratchets in order and keeps the first

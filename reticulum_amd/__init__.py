@@ -12,7 +12,12 @@ Batch use: ``KeySet.encrypt_batch`` / ``decrypt_batch`` over host buffers,
 ``reticulum_amd.shard`` for one-process-per-GPU sharding.  Key derivation:
 ``hkdf`` (drop-in for RNS.Cryptography.hkdf), ``hkdf_batch`` and
 ``derive_keyset`` (Identity's per-packet keys, derived and expanded on the
-device).  Resource hashmaps: ``resource_hashmap`` / ``build_hashmap`` /
+device).  X25519: ``exchange_batch`` / ``public_keys_batch`` / ``exchange`` /
+``public_key`` (``reticulum_amd.x25519``, X25519.py:49-93); Identity.encrypt /
+decrypt for a batch, from the exchange to the token: ``encrypt_batch`` /
+``decrypt_batch`` (``reticulum_amd.identity``, Identity.py:803-904); their
+device-tensor forms are ``device.x25519`` and ``device.derive_keyset_x25519``.
+Resource hashmaps: ``resource_hashmap`` / ``build_hashmap`` /
 ``get_map_hash`` (Resource.py:426-468, 505-506); integrity hash and proof:
 ``resource_hashes`` / ``verify_resource`` / ``validate_proof`` /
 ``prepare_resource`` (Resource.py:436-439, 698-699, 759-760, 787-790).  Wire-side neighbours
@@ -25,6 +30,9 @@ which raises ImportError when they are not.
 from ._native import NativeError, NativeUnavailable, LIB_PATH, available  # noqa: F401
 from ._native import RT_ST_OK, RT_ST_TOO_SHORT, RT_ST_BAD_HMAC, RT_ST_BAD_CT_LEN, RT_ST_BAD_PAD  # noqa: F401
 from .hkdf import derive_keyset, hkdf, hkdf_batch  # noqa: F401
+from . import identity, x25519  # noqa: F401
+from .identity import decrypt_batch, encrypt_batch  # noqa: F401
+from .x25519 import exchange, exchange_batch, public_key, public_keys_batch  # noqa: F401
 from .resource import build_hashmap, get_map_hash, resource_hashmap  # noqa: F401
 from .resource import prepare_resource, resource_hashes, validate_proof, verify_resource  # noqa: F401
 from . import wire  # noqa: F401

@@ -52,6 +52,9 @@ SIGNATURES = [
     ("rt_hkdf", _int, [_vp, _vp, _u64, _u32, _vp, _u64, _u32, _vp, _u32, _vp, _u64, _u32, _u32, _vp]),
     ("rt_hkdf_host", _int, [_vp, _vp, _u64, _u32, _vp, _u64, _u32, _vp, _u32, _vp, _u64, _u32, _u32]),
     ("rt_keyset_create_hkdf", _vp, [_vp, _vp, _u64, _u32, _vp, _u64, _u32, _vp, _u32, _u32, _u32, _vp]),
+    ("rt_x25519", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32, _vp]),
+    ("rt_x25519_host", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32]),
+    ("rt_keyset_create_x25519", _vp, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u32, _u32, _u32, _vp]),
     ("rt_verify_trials", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     ("rt_verify_trials_host", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     ("rt_map_hashes", _int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp]),

@@ -1166,6 +1166,24 @@ int rt_hkdf_host(rt_ctx *c, const uint8_t *ikm, uint64_t ikm_stride, uint32_t ik
     return RT_OK;
 }
 
+// Enqueues on s the kernels that write k's records from the keys `a` derives
+// (a.length = the key length, a.out unused).
+static hipError_t hkdf_records(rt_ctx *c, const HkdfArgs &a, rt_keyset *k, hipStream_t s) {
+    // one launch: derive each key in registers and build its record
+    hipError_t e = launch_hkdf_key_setup(a, c->d_sbox, k->d_rec, c->n_cu, s);
+    if (e != hipErrorNotSupported) return e;
+    // other shapes (context, long or unaligned ikm/salt): HKDF into a
+    // stream-ordered temporary, then the key setup
+    uint8_t *d_keys = nullptr;
+    if ((e = hipMallocAsync((void **)&d_keys, (uint64_t)a.n * a.length, s)) != hipSuccess) return e;
+    HkdfArgs t = a;
+    t.out = d_keys;
+    e = launch_hkdf(t, s);
+    if (e == hipSuccess) e = launch_key_setup(d_keys, a.length, a.n, c->d_sbox, k->d_rec, s);
+    hipFreeAsync(d_keys, s);     // freed after the key setup has consumed it
+    return e;
+}
+
 rt_keyset *rt_keyset_create_hkdf(rt_ctx *c, const uint8_t *ikm, uint64_t ikm_stride, uint32_t ikm_len,
                                  const uint8_t *salt, uint64_t salt_stride, uint32_t salt_len,
                                  const uint8_t *context, uint32_t context_len, uint32_t key_len, uint32_t n,
@@ -1183,19 +1201,101 @@ rt_keyset *rt_keyset_create_hkdf(rt_ctx *c, const uint8_t *ikm, uint64_t ikm_str
     hipStream_t s = pick(c, stream);
     const HkdfArgs a = hkdf_args(ikm, ikm_stride, ikm_len, salt, salt_stride, salt_len, context, context_len, nullptr,
                                  key_len, key_len, n);
+    return keyset_on(c, key_len, n, s, [&](rt_keyset *k) { return hkdf_records(c, a, k, s); });
+}
+
+// ---------------------------------------------------------------- X25519 --
+
+static int x25519_check(rt_ctx *c, const uint8_t *scalars, uint64_t scalar_stride, const uint8_t *points,
+                        uint64_t point_stride, const uint64_t *point_off) {
+    if (!c) return fail(RT_E_INVAL, "null context");
+    if (!scalars) return fail(RT_E_INVAL, "rt_x25519: null scalars");
+    if (point_off && !points) return fail(RT_E_INVAL, "rt_x25519: point_off without points");
+    if ((scalar_stride && scalar_stride < 32) || (points && !point_off && point_stride && point_stride < 32))
+        return fail(RT_E_INVAL, "rt_x25519: a stride is 0 (one row for all) or at least 32");
+    return RT_OK;
+}
+
+int rt_x25519(rt_ctx *c, const uint8_t *scalars, uint64_t scalar_stride, const uint8_t *points, uint64_t point_stride,
+              const uint64_t *point_off, uint8_t *out, uint64_t out_stride, uint32_t n, void *stream) {
+    int rc = x25519_check(c, scalars, scalar_stride, points, point_stride, point_off);
+    if (rc || n == 0) return rc;
+    if (!out) return fail(RT_E_INVAL, "rt_x25519: null output");
+    if (out_stride < 32 && n > 1) return fail(RT_E_INVAL, "rt_x25519: out_stride smaller than 32");
+    RT_HIP(hipSetDevice(c->device), "hipSetDevice");
+    const X25519Args a{scalars, scalar_stride, points, point_stride, point_off, out, out_stride, n};
+    RT_HIP(launch_x25519(a, pick(c, stream)), "x25519 launch");
+    return RT_OK;
+}
+
+int rt_x25519_host(rt_ctx *c, const uint8_t *scalars, uint64_t scalar_stride, const uint8_t *points,
+                   uint64_t point_stride, const uint64_t *point_off, uint8_t *out, uint64_t out_stride, uint32_t n) {
+    int rc = x25519_check(c, scalars, scalar_stride, points, point_stride, point_off);
+    if (rc || n == 0) return rc;
+    if (!out) return fail(RT_E_INVAL, "rt_x25519: null output");
+    if (out_stride < 32 && n > 1) return fail(RT_E_INVAL, "rt_x25519: out_stride smaller than 32");
+    // packed rows on the device: scalars (n or 1) x 32, points (n or 1) x 32, out n x 32
+    const uint64_t n_sc = scalar_stride ? n : 1u, n_pt = !points ? 0u : (point_off || point_stride) ? n : 1u;
+    const uint64_t o_sc = 0, o_pt = align16(o_sc + 32 * n_sc), o_out = align16(o_pt + 32 * n_pt),
+                   total = o_out + 32ull * n;
+    std::vector<uint8_t> gathered;     // rows named by point_off, packed (alive until the sync below)
+    if (point_off) {
+        gathered.resize(32ull * n);
+        for (uint32_t i = 0; i < n; ++i) memcpy(&gathered[32ull * i], points + point_off[i], 32);
+    }
+    StageLock L(c);
+    Stager &g = *L.g;
+    RT_HIP(hipSetDevice(c->device), "hipSetDevice");
+    if ((rc = ensure_work(g, total))) return rc;
+    uint8_t *w = g.d_work;
+    hipStream_t s = g.stream;
+    RT_HIP(hipMemcpy2DAsync(w + o_sc, 32, scalars, scalar_stride ? scalar_stride : 32, 32, n_sc, hipMemcpyHostToDevice, s),
+           "H2D scalars");
+    if (point_off)
+        RT_HIP(hipMemcpyAsync(w + o_pt, gathered.data(), 32ull * n, hipMemcpyHostToDevice, s), "H2D points");
+    else if (n_pt)
+        RT_HIP(hipMemcpy2DAsync(w + o_pt, 32, points, point_stride ? point_stride : 32, 32, n_pt, hipMemcpyHostToDevice, s),
+               "H2D points");
+    const X25519Args a{w + o_sc, scalar_stride ? 32u : 0u, n_pt ? w + o_pt : nullptr, n_pt > 1 ? 32u : 0u,
+                       nullptr, w + o_out, 32, n};
+    RT_HIP(launch_x25519(a, s), "x25519 launch");
+    RT_HIP(hipMemcpy2DAsync(out, out_stride < 32 ? 32 : out_stride, w + o_out, 32, 32, n, hipMemcpyDeviceToHost, s),
+           "D2H out");
+    RT_HIP(hipStreamSynchronize(s), "stream sync");
+    return RT_OK;
+}
+
+rt_keyset *rt_keyset_create_x25519(rt_ctx *c, const uint8_t *scalars, uint64_t scalar_stride, const uint8_t *points,
+                                   uint64_t point_stride, const uint64_t *point_off, const uint8_t *salt,
+                                   uint64_t salt_stride, uint32_t salt_len, const uint8_t *context,
+                                   uint32_t context_len, uint32_t key_len, uint32_t n, void *stream) {
+    if (x25519_check(c, scalars, scalar_stride, points, point_stride, point_off)) return nullptr;
+    if (context_len && !context) {
+        fail(RT_E_INVAL, "rt_keyset_create_x25519: null context bytes");
+        return nullptr;
+    }
+    if (n == 0) {
+        fail(RT_E_INVAL, "rt_keyset_create_x25519: zero keys");
+        return nullptr;
+    }
+    if (key_len != 64 && key_len != 32) {   // Token.py:72
+        fail(RT_E_INVAL, "Token key must be 128 or 256 bits, not " + std::to_string(key_len * 8));
+        return nullptr;
+    }
+    hipSetDevice(c->device);
+    hipStream_t s = pick(c, stream);
     return keyset_on(c, key_len, n, s, [&](rt_keyset *k) {
-        // one launch: derive each key in registers and build its record
-        hipError_t e = launch_hkdf_key_setup(a, c->d_sbox, k->d_rec, c->n_cu, s);
-        if (e != hipErrorNotSupported) return e;
-        // other shapes (context, long or unaligned ikm/salt): HKDF into a
-        // stream-ordered temporary, then the key setup
-        uint8_t *d_keys = nullptr;
-        if ((e = hipMallocAsync((void **)&d_keys, (uint64_t)n * key_len, s)) != hipSuccess) return e;
-        HkdfArgs t = a;
-        t.out = d_keys;
-        e = launch_hkdf(t, s);
-        if (e == hipSuccess) e = launch_key_setup(d_keys, key_len, n, c->d_sbox, k->d_rec, s);
-        hipFreeAsync(d_keys, s);     // freed after the key setup has consumed it
+        // the shared secrets live in a stream-ordered temporary: written by
+        // the exchange, read by the key derivation, freed after it
+        uint8_t *d_shared = nullptr;
+        hipError_t e = hipMallocAsync((void **)&d_shared, 32ull * n, s);
+        if (e != hipSuccess) return e;
+        const X25519Args x{scalars, scalar_stride, points, point_stride, point_off, d_shared, 32, n};
+        e = launch_x25519(x, s);
+        if (e == hipSuccess)
+            e = hkdf_records(c, hkdf_args(d_shared, 32, 32, salt, salt_stride, salt_len, context, context_len, nullptr,
+                                          key_len, key_len, n), k, s);
+        hipFreeAsync(d_shared, s);
         return e;
     });
 }

@@ -79,6 +79,22 @@ struct HkdfArgs {
     uint32_t n;
 };
 
+// X25519 over n items (x25519_kernels.hip): out_i = X25519(scalar_i, point_i),
+// scalar_i at scalars + i*scalar_stride, point_i at points + point_off[i]
+// (point_off null: points + i*point_stride; points null: the base point 9),
+// 32 bytes at out + i*out_stride.  Strides of 0 share one row.
+struct X25519Args {
+    const uint8_t *scalars;
+    uint64_t scalar_stride;
+    const uint8_t *points;
+    uint64_t point_stride;
+    const uint64_t *point_off;
+    uint8_t *out;
+    uint64_t out_stride;
+    uint32_t n;
+};
+hipError_t launch_x25519(const X25519Args &a, hipStream_t s);
+
 // Resource map hashes (resource_kernels.hip): part j = data + part_off[j]
 // (part_len[j] bytes), or with part_off null the uniform segmentation
 // data[j*sdu, min((j+1)*sdu, size)); salt = salts + part_res[j]*salt_len.

@@ -349,6 +349,84 @@ def derive_keyset(ikm, salt=None, context=None, key_len=64, stream=None):
     return KeySet._adopt(h, key_len, n, lib, ctx)
 
 
+def _x25519_rows(name, t, n):
+    """(pointer, row stride) of 32-byte rows: an (n, >=32) uint8 matrix whose
+    rows sit at any stride >= 32, or one row for all n items (shape (1, 32),
+    or expanded to (n, 32) with row stride 0)."""
+    if not t.is_cuda:
+        raise ValueError("device API needs tensors in device memory")
+    if t.dim() != 2 or t.shape[1] < 32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name} must be an (n, 32) uint8 matrix with contiguous rows")
+    if t.shape[0] == 1 or (t.shape[0] == n and t.stride(0) == 0):
+        return t.data_ptr(), 0
+    if t.shape[0] != n or t.stride(0) < 32:
+        raise ValueError(f"{name} must hold {n} rows (or one row for all) at a stride of at least 32")
+    return t.data_ptr(), t.stride(0)
+
+
+def _x25519_args(scalars, points, point_off, n):
+    _check_u8(scalars, points)
+    p_sc, s_sc = _x25519_rows("scalars", scalars, n)
+    if point_off is not None:
+        if points is None:
+            raise ValueError("point_off needs points")
+        _check_i64(n, point_off=point_off)
+        return p_sc, s_sc, _p(points), 0, _p(point_off)
+    if points is None:
+        return p_sc, s_sc, None, 0, None
+    p_pt, s_pt = _x25519_rows("points", points, n)
+    return p_sc, s_sc, p_pt, s_pt, None
+
+
+def x25519(scalars, points, out, point_off=None, stream=None):
+    """X25519 over device rows (RNS/Cryptography/X25519.py:49-93): row i of
+    out (n, >=32 uint8, any row stride) = X25519(scalars[i], points[i]).
+    scalars and points are (n, 32) uint8 rows at any stride >= 32, or one row
+    for all (shape (1, 32) or expanded with stride 0: the receiver's key, the
+    sender's target key); points None is the base point (public keys); with
+    point_off ((n,) int64) points is a flat byte buffer and point i the 32
+    bytes at points[point_off[i]:], e.g. the head of each token."""
+    _check_u8(out)
+    if out.dim() != 2 or out.shape[1] < 32 or (out.shape[1] > 1 and out.stride(1) != 1) or \
+            (out.shape[0] > 1 and out.stride(0) < 32):
+        raise ValueError("out must be an (n, >=32) uint8 matrix with contiguous rows")
+    n = out.shape[0]
+    sc, sc_stride, pt, pt_stride, off = _x25519_args(scalars, points, point_off, n)
+    lib = _native.load()
+    ctx = _native.context(out.device.index)
+    _native.check(lib.rt_x25519(ctx, sc, sc_stride, pt, pt_stride, off, _p_rows(out), max(out.stride(0), 32), n,
+                                _stream(stream, out.device)))
+
+
+def derive_keyset_x25519(scalars, points, salt=None, context=None, key_len=64, point_off=None, n=None, stream=None):
+    """Identity's per-packet keying from the exchange on (Identity.py:812-829,
+    861-871): KeySet whose key i is Token(hkdf(key_len, X25519(scalars[i],
+    points[i]), salt[i], context)) for i < n; scalars, points and point_off
+    as :func:`x25519`, salt and context as :func:`derive_keyset`.  n defaults
+    to the number of offsets, else of scalar or point rows.  The shared
+    secrets and the derived keys stay on the device."""
+    if key_len not in (32, 64):
+        raise ValueError("Token key must be 128 or 256 bits, not " + str(key_len * 8))
+    _check_u8(salt, context)
+    if n is None:
+        n = point_off.numel() if point_off is not None else \
+            max(scalars.shape[0], points.shape[0] if points is not None else 1)
+    sc, sc_stride, pt, pt_stride, off = _x25519_args(scalars, points, point_off, n)
+    if salt is not None and (salt.dim() != 2 or salt.shape[0] != n):
+        raise ValueError(f"salt must be an ({n}, S) uint8 matrix (one row may be expanded)")
+    lib = _native.load()
+    ctx = _native.context(scalars.device.index)
+    _order_after_current(stream, scalars, points, point_off, salt, context)
+    h = lib.rt_keyset_create_x25519(ctx, sc, sc_stride, pt, pt_stride, off, _p_salt(salt),
+                                    salt.stride(0) if salt is not None else 0,
+                                    salt.shape[1] if salt is not None else 0, _p(context),
+                                    context.numel() if context is not None else 0, key_len, n,
+                                    _stream(stream, scalars.device))
+    if not h:
+        raise _native.NativeError(-1, _native.last_error())
+    return KeySet._adopt(h, key_len, n, lib, ctx)
+
+
 def map_hashes(data, out, salts, part_off=None, part_len=None, part_res=None, sdu=464, guard=0,
                first_collision=None, stream=None):
     """Resource map hashes over device buffers (Resource.py:505-506): out
