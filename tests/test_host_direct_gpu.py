@@ -2,7 +2,7 @@
 (Token.py:87-114, called per packet from Link.py:1161-1182): rt_encrypt_host /
 rt_decrypt_host with n = 1 run the token kernel on the staging lane's mapped
 pinned buffer itself, with no copy kernel in and no store kernel out
-(host_direct, csrc/token_capi.hip).
+(host_direct: HostCall::open(true), csrc/capi_token.hip).
 
 Bit-exact against the C oracle over a length sweep on one key set (each call's
 inputs replace the previous call's in the same staging buffer, so stale data
