@@ -33,6 +33,8 @@
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
+ *   rt_ed25519_*       Ed25519 verify / sign / public key  RNS/Cryptography/pure25519/eddsa.py,
+ *                                                Identity.validate, Identity.sign, validate_announce
  *   rt_keyset_create_x25519  the same keying from the exchange on: Identity.py:812-829, 861-871
  *   rt_verify_trials*  ratchet trial loop       Identity.py:865-878 (first ratchet whose key
  *                                                opens the token; Token.py:77-84,114)
@@ -282,6 +284,60 @@ rt_keyset *rt_keyset_create_x25519(rt_ctx *ctx, const uint8_t *scalars, uint64_t
                                    const uint8_t *salt, uint64_t salt_stride, uint32_t salt_len,
                                    const uint8_t *context, uint32_t context_len, uint32_t key_len, uint32_t n,
                                    void *stream);
+
+/* ---- Ed25519 (RNS/Cryptography/pure25519/eddsa.py, basic.py) ------------ */
+/* n independent items, one per lane.  Item i's message is the msg_len[i]
+ * bytes at msgs + msg_off[i] (uint64 offsets, uint32 lengths, n each; any
+ * alignment; offsets may repeat and come in any order); msgs == NULL is
+ * accepted only when every length is 0 (the _host calls check that; the device
+ * calls cannot, and take every message as empty then).  Keys and seeds are 32 bytes at
+ * base + i*stride, signatures 64 bytes; stride 0 means one row for all items
+ * (one identity's key against many proofs), a non-zero key or seed stride is
+ * at least 32, sig_stride and out_stride are at least 64 when n > 1.  A NULL
+ * required pointer is RT_E_INVAL; n == 0 is RT_OK.  The plain calls take
+ * DEVICE pointers and only enqueue on `stream`; the _host calls take HOST
+ * pointers and return when the output is filled.
+ *
+ * Results follow the reference's internal provider (pure25519), which is what
+ * Reticulum runs where PyCA is absent; a PyCA-backed node differs on the
+ * marked lines (*).  rt_ed25519_verify writes ok[i] = 1 where eddsa.checkvalid
+ * returns True and 0 where it returns False or raises:
+ *   - the key and R (sig[:32]) must not be the canonical encoding of the
+ *     identity, 01 00 .. 00; other encodings of it pass this test;
+ *   - both must decode: y is the low 255 bits, taken mod p and not required
+ *     to be below p; x = xrecover(y) must satisfy the curve equation; x is
+ *     negated where its parity differs from bit 255 (x = 0 with the bit set
+ *     stays 0);
+ *   - [L]A and [L]R must be the identity: small-order and mixed-order points
+ *     are rejected even where the cofactorless equation holds (*);
+ *   - S is any 256-bit integer and is used mod L, so S >= L is accepted (*);
+ *     h = SHA-512(R || A || M) as a little-endian integer mod L;
+ *   - [S mod L]B = R + [h mod L]A as points, whatever R's encoding;
+ *   - a key that is the identity in a non-canonical encoding is rejected
+ *     unless h mod L = 0 (the reference's subgroup multiplication does not
+ *     hold for it).
+ * rt_ed25519_sign is eddsa.signature: h = SHA-512(seed), a = clamp(h[:32]),
+ * r = SHA-512(h[32:] || M) mod L, R = [r]B, S = (r + SHA-512(R || A || M) a)
+ * mod L, output enc(R) || S.  pubs == NULL: A = enc([a]B) is derived per item;
+ * else A is read from pubs and trusted.  rt_ed25519_public writes enc([a]B).
+ * Signing and public keys are constant time: no branch, loop bound or address
+ * depends on the seed or on a value derived from it. */
+int rt_ed25519_verify(rt_ctx *ctx, const uint8_t *pubs, uint64_t pub_stride, const uint8_t *sigs,
+                      uint64_t sig_stride, const uint8_t *msgs, const uint64_t *msg_off, const uint32_t *msg_len,
+                      uint8_t *ok, uint32_t n, void *stream);
+int rt_ed25519_verify_host(rt_ctx *ctx, const uint8_t *pubs, uint64_t pub_stride, const uint8_t *sigs,
+                           uint64_t sig_stride, const uint8_t *msgs, const uint64_t *msg_off,
+                           const uint32_t *msg_len, uint8_t *ok, uint32_t n);
+int rt_ed25519_sign(rt_ctx *ctx, const uint8_t *seeds, uint64_t seed_stride, const uint8_t *pubs,
+                    uint64_t pub_stride, const uint8_t *msgs, const uint64_t *msg_off, const uint32_t *msg_len,
+                    uint8_t *sigs_out, uint64_t out_stride, uint32_t n, void *stream);
+int rt_ed25519_sign_host(rt_ctx *ctx, const uint8_t *seeds, uint64_t seed_stride, const uint8_t *pubs,
+                         uint64_t pub_stride, const uint8_t *msgs, const uint64_t *msg_off,
+                         const uint32_t *msg_len, uint8_t *sigs_out, uint64_t out_stride, uint32_t n);
+int rt_ed25519_public(rt_ctx *ctx, const uint8_t *seeds, uint64_t seed_stride, uint8_t *out, uint64_t out_stride,
+                      uint32_t n, void *stream);
+int rt_ed25519_public_host(rt_ctx *ctx, const uint8_t *seeds, uint64_t seed_stride, uint8_t *out,
+                           uint64_t out_stride, uint32_t n);
 
 /* ---- ratchet trials (Identity.decrypt, RNS/Identity.py:865-878) --------- */
 /* Identity.decrypt tries the receiver's ratchets in order and keeps the first

@@ -17,6 +17,11 @@ device).  X25519: ``exchange_batch`` / ``public_keys_batch`` / ``exchange`` /
 decrypt for a batch, from the exchange to the token: ``encrypt_batch`` /
 ``decrypt_batch`` (``reticulum_amd.identity``, Identity.py:803-904); their
 device-tensor forms are ``device.x25519`` and ``device.derive_keyset_x25519``.
+Ed25519 (``reticulum_amd.ed25519``: ``verify_batch`` / ``sign_batch`` /
+``public_keys_batch`` and the single forms, as the reference's internal
+provider decides); ``Identity.validate`` / ``sign`` / ``validate_announce``
+for a batch: ``validate_batch`` / ``sign_batch`` / ``validate_announces_batch``;
+device-tensor forms ``device.ed25519_verify`` / ``ed25519_sign`` / ``ed25519_public``.
 Resource hashmaps: ``resource_hashmap`` / ``build_hashmap`` /
 ``get_map_hash`` (Resource.py:426-468, 505-506); integrity hash and proof:
 ``resource_hashes`` / ``verify_resource`` / ``validate_proof`` /
@@ -30,8 +35,9 @@ which raises ImportError when they are not.
 from ._native import NativeError, NativeUnavailable, LIB_PATH, available  # noqa: F401
 from ._native import RT_ST_OK, RT_ST_TOO_SHORT, RT_ST_BAD_HMAC, RT_ST_BAD_CT_LEN, RT_ST_BAD_PAD  # noqa: F401
 from .hkdf import derive_keyset, hkdf, hkdf_batch  # noqa: F401
-from . import identity, x25519  # noqa: F401
+from . import ed25519, identity, x25519  # noqa: F401
 from .identity import decrypt_batch, encrypt_batch  # noqa: F401
+from .identity import sign_batch, validate_announces_batch, validate_batch  # noqa: F401
 from .x25519 import exchange, exchange_batch, public_key, public_keys_batch  # noqa: F401
 from .resource import build_hashmap, get_map_hash, resource_hashmap  # noqa: F401
 from .resource import prepare_resource, resource_hashes, validate_proof, verify_resource  # noqa: F401

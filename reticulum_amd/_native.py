@@ -55,6 +55,12 @@ SIGNATURES = [
     ("rt_x25519", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32, _vp]),
     ("rt_x25519_host", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32]),
     ("rt_keyset_create_x25519", _vp, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _u32, _u32, _u32, _vp]),
+    ("rt_ed25519_verify", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp]),
+    ("rt_ed25519_verify_host", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u32]),
+    ("rt_ed25519_sign", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u32, _vp]),
+    ("rt_ed25519_sign_host", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u32]),
+    ("rt_ed25519_public", _int, [_vp, _vp, _u64, _vp, _u64, _u32, _vp]),
+    ("rt_ed25519_public_host", _int, [_vp, _vp, _u64, _vp, _u64, _u32]),
     ("rt_verify_trials", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     ("rt_verify_trials_host", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     ("rt_map_hashes", _int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _u32, _vp]),

@@ -95,6 +95,44 @@ struct X25519Args {
 };
 hipError_t launch_x25519(const X25519Args &a, hipStream_t s);
 
+// Ed25519 over n items (ed25519_kernels.hip).  Item i's key is at pubs +
+// i*pub_stride (32 bytes), its signature at sigs + i*sig_stride (64 bytes), its
+// message at msgs + msg_off[i] (msg_len[i] bytes, any alignment; never read
+// where msg_len[i] is 0).  Strides of 0 share one row.
+struct Ed25519VerifyArgs {
+    const uint8_t *pubs;
+    uint64_t pub_stride;
+    const uint8_t *sigs;
+    uint64_t sig_stride;
+    const uint8_t *msgs;
+    const uint64_t *msg_off;
+    const uint32_t *msg_len;
+    uint8_t *ok;                   // 1 accepted, 0 rejected
+    uint32_t n;
+};
+struct Ed25519SignArgs {
+    const uint8_t *seeds;
+    uint64_t seed_stride;
+    const uint8_t *pubs;           // null: each lane derives its public key
+    uint64_t pub_stride;
+    const uint8_t *msgs;
+    const uint64_t *msg_off;
+    const uint32_t *msg_len;
+    uint8_t *out;                  // 64 bytes at out + i*out_stride
+    uint64_t out_stride;
+    uint32_t n;
+};
+struct Ed25519PublicArgs {
+    const uint8_t *seeds;
+    uint64_t seed_stride;
+    uint8_t *out;                  // 32 bytes at out + i*out_stride
+    uint64_t out_stride;
+    uint32_t n;
+};
+hipError_t launch_ed25519_verify(const Ed25519VerifyArgs &a, hipStream_t s);
+hipError_t launch_ed25519_sign(const Ed25519SignArgs &a, hipStream_t s);
+hipError_t launch_ed25519_public(const Ed25519PublicArgs &a, hipStream_t s);
+
 // Resource map hashes (resource_kernels.hip): part j = data + part_off[j]
 // (part_len[j] bytes), or with part_off null the uniform segmentation
 // data[j*sdu, min((j+1)*sdu, size)); salt = salts + part_res[j]*salt_len.

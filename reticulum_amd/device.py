@@ -475,6 +475,89 @@ def resource_hashes(data, seg_off, seg_len, random_hashes, hash_out, proof_out=N
                                          _p(proof_out), _p(status), n, _stream(stream, data.device)))
 
 
+# ------------------------------------------------------------------ Ed25519 --
+# Device-resident forms of reticulum_amd.ed25519 (ed25519_kernels.hip): rows as
+# in x25519, messages as a flat uint8 buffer with int64 offsets and int32
+# lengths like the wire functions; enqueued on the stream, no sync.
+
+def _ed_rows(name, t, n, width):
+    """(pointer, row stride) of `width`-byte rows at any stride >= width, or
+    one row for all n items (shape (1, width), or expanded with stride 0)."""
+    if not t.is_cuda:
+        raise ValueError("device API needs tensors in device memory")
+    if t.dim() != 2 or t.shape[1] < width or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name} must be an (n, {width}) uint8 matrix with contiguous rows")
+    if t.shape[0] == 1 or (t.shape[0] == n and t.stride(0) == 0):
+        return t.data_ptr(), 0
+    if t.shape[0] != n or t.stride(0) < width:
+        raise ValueError(f"{name} must hold {n} rows (or one row for all) at a stride of at least {width}")
+    return t.data_ptr(), t.stride(0)
+
+
+def _ed_msgs(msgs, msg_off, msg_len, n):
+    _check_u8(msgs)
+    _check_i64(n, msg_off=msg_off)
+    _check_i32(n, msg_len=msg_len)
+    if msg_off is None or msg_len is None:
+        raise ValueError("msg_off and msg_len are required")
+    return (_p(msgs) if msgs is not None and msgs.numel() else None), _p(msg_off), _p(msg_len)
+
+
+def ed25519_verify(public_keys, signatures, msgs, msg_off, msg_len, ok, stream=None):
+    """Ed25519 verification over device rows (pure25519/eddsa.py checkvalid):
+    ok[i] ((n,) uint8) = 1 where signatures[i] ((n, 64) rows at any stride
+    >= 64) is public_keys[i]'s ((n, 32) rows, or one row for all) signature of
+    the msg_len[i] bytes at msgs[msg_off[i]:], else 0.  msgs None or empty:
+    every message is empty."""
+    _check_u8(public_keys, signatures, ok)
+    n = ok.numel()
+    if not ok.is_contiguous():
+        raise ValueError("ok must be a contiguous (n,) uint8 tensor")
+    pk, pk_stride = _ed_rows("public_keys", public_keys, n, 32)
+    sg, sg_stride = _ed_rows("signatures", signatures, n, 64)
+    if n > 1 and sg_stride == 0:
+        raise ValueError("signatures must hold one row per item")
+    m, off, ln = _ed_msgs(msgs, msg_off, msg_len, n)
+    lib = _native.load()
+    ctx = _native.context(ok.device.index)
+    _native.check(lib.rt_ed25519_verify(ctx, pk, pk_stride, sg, max(sg_stride, 64), m, off, ln, _p(ok), n,
+                                        _stream(stream, ok.device)))
+
+
+def ed25519_sign(seeds, msgs, msg_off, msg_len, out, public_keys=None, stream=None):
+    """Ed25519 signatures over device rows (pure25519/eddsa.py signature): row
+    i of out ((n, >=64) uint8, any row stride) = the signature of message i
+    under seeds[i] ((n, 32) rows, or one row for all).  public_keys (the
+    seeds', trusted) spares the kernel their derivation."""
+    _check_u8(seeds, out, public_keys)
+    if out.dim() != 2 or out.shape[1] < 64 or (out.shape[1] > 1 and out.stride(1) != 1) or \
+            (out.shape[0] > 1 and out.stride(0) < 64):
+        raise ValueError("out must be an (n, >=64) uint8 matrix with contiguous rows")
+    n = out.shape[0]
+    sd, sd_stride = _ed_rows("seeds", seeds, n, 32)
+    pk, pk_stride = (None, 0) if public_keys is None else _ed_rows("public_keys", public_keys, n, 32)
+    m, off, ln = _ed_msgs(msgs, msg_off, msg_len, n)
+    lib = _native.load()
+    ctx = _native.context(out.device.index)
+    _native.check(lib.rt_ed25519_sign(ctx, sd, sd_stride, pk, pk_stride, m, off, ln, _p_rows(out),
+                                      max(out.stride(0), 64), n, _stream(stream, out.device)))
+
+
+def ed25519_public(seeds, out, stream=None):
+    """Ed25519 public keys over device rows: row i of out ((n, >=32) uint8, any
+    row stride) = the public key of seeds[i]."""
+    _check_u8(seeds, out)
+    if out.dim() != 2 or out.shape[1] < 32 or (out.shape[1] > 1 and out.stride(1) != 1) or \
+            (out.shape[0] > 1 and out.stride(0) < 32):
+        raise ValueError("out must be an (n, >=32) uint8 matrix with contiguous rows")
+    n = out.shape[0]
+    sd, sd_stride = _ed_rows("seeds", seeds, n, 32)
+    lib = _native.load()
+    ctx = _native.context(out.device.index)
+    _native.check(lib.rt_ed25519_public(ctx, sd, sd_stride, _p_rows(out), max(out.stride(0), 32), n,
+                                        _stream(stream, out.device)))
+
+
 # ---------------------------------------------------------------- wire side --
 # Device-resident forms of reticulum_amd.wire (wire_kernels.hip): flat uint8
 # buffers, int64 offsets, int32 lengths, enqueued on the stream, no sync.

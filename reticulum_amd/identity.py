@@ -10,11 +10,12 @@ setup kernel, and the token in the encrypt / decrypt kernels; the shared
 secrets and the derived keys never leave the device.  No CPU fallback.
 """
 import ctypes
+import hashlib
 import os
 
 import numpy as np
 
-from . import _native, x25519
+from . import _native, ed25519, x25519
 from ._native import RT_ST_OK
 from .token import KeySet, Packed
 
@@ -141,3 +142,86 @@ def decrypt_batch(private, salt, tokens, ratchets=None, enforce_ratchets=False, 
             r = int(key_used[j]) - j * C
             plaintexts[i], which[i] = out[j], (r if r < R else -1)
     return plaintexts, which
+
+
+# ------------------------------------------------- signatures (Ed25519) -----
+
+def validate_batch(sig_public, signatures, messages, device=None):
+    """``Identity.validate`` (Identity.py:924-940) over a batch: a list of
+    bools, element i telling whether ``signatures[i]`` is the signature of
+    ``messages[i]`` under the 32-byte Ed25519 key ``sig_public`` (bytes: one
+    identity; or one key per message).  A signature that is not 64 bytes long
+    gives False and does not raise: the reference's assertion is swallowed by
+    ``validate``'s ``except``."""
+    sigs, msgs = list(signatures), list(messages)
+    if len(sigs) != len(msgs):
+        raise ValueError("need one signature per message")
+    for v in sigs:
+        if not isinstance(v, (bytes, bytearray, memoryview)):
+            raise TypeError("signatures must be bytes")
+    one_key = isinstance(sig_public, (bytes, bytearray, memoryview))
+    keys = sig_public if one_key else list(sig_public)
+    if not one_key and len(keys) != len(msgs):
+        raise ValueError("need one public key per message (or one bytes object to broadcast)")
+    keep = [i for i, v in enumerate(sigs) if len(v) == 64]
+    out = [False] * len(msgs)
+    if one_key or keep:
+        ok = ed25519.verify_batch(keys if one_key else [keys[i] for i in keep], [sigs[i] for i in keep],
+                                  [msgs[i] for i in keep], device)
+        for i, v in zip(keep, ok):
+            out[i] = bool(v)
+    return out
+
+
+def sign_batch(sig_private, messages, device=None):
+    """``Identity.sign`` (Identity.py:907-922) over a batch: the 64-byte
+    signatures of ``messages`` under the 32-byte Ed25519 seed ``sig_private``
+    (the second half of ``Identity.get_private_key()``), as a list of bytes.
+    The public key is derived once and handed to the signing kernel."""
+    msgs = list(messages)
+    if not isinstance(sig_private, (bytes, bytearray, memoryview)):
+        raise TypeError("signing key must be bytes")
+    if len(sig_private) != 32:
+        raise ValueError(ed25519.BAD_SIGNING_KEY % len(sig_private))
+    for m in msgs:
+        if not isinstance(m, (bytes, bytearray, memoryview)):
+            raise TypeError("messages must be bytes")
+    if not msgs:
+        return []
+    pub = ed25519.public_key(sig_private, device)
+    return [row.tobytes() for row in ed25519.sign_batch(sig_private, msgs, public_keys=pub, device=device)]
+
+
+def validate_announces_batch(announces, only_validate_signature=False, device=None):
+    """``Identity.validate_announce`` (Identity.py:511-606) over a batch of
+    ``(destination_hash, context_flag, data)``: a list of bools.  The fields
+    are cut as the reference cuts them (64-byte public key, 10-byte name hash,
+    10-byte random hash, a 32-byte ratchet when the context flag is set, the
+    64-byte signature, app data), the signatures over destination_hash ‖
+    public_key ‖ name_hash ‖ random_hash ‖ ratchet ‖ app_data are verified on
+    the device under ``data[32:64]``, and unless ``only_validate_signature``
+    the destination hash must be that of the name hash and the announced
+    identity.  Data too short for its fixed fields gives False.  Remembering
+    destinations and ratchets, blackholed identities and logging stay with
+    the caller."""
+    items = list(announces)
+    out = [False] * len(items)
+    keep, keys, sigs, signed = [], [], [], []
+    for i, (destination_hash, context_flag, data) in enumerate(items):
+        data = bytes(data)
+        head = 116 if context_flag else 84            # key 64, name hash 10, random hash 10, ratchet 32
+        if len(data) < head + 64:
+            continue
+        public_key, signature, app_data = data[:64], data[head:head + 64], data[head + 64:]
+        if not only_validate_signature:
+            identity_hash = hashlib.sha256(public_key).digest()[:16]
+            if bytes(destination_hash) != hashlib.sha256(data[64:74] + identity_hash).digest()[:16]:
+                continue
+        keep.append(i)
+        keys.append(public_key[32:])
+        sigs.append(signature)
+        signed.append(bytes(destination_hash) + data[:head] + app_data)
+    if keep:
+        for i, v in zip(keep, ed25519.verify_batch(keys, sigs, signed, device)):
+            out[i] = bool(v)
+    return out
