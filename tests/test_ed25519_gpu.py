@@ -8,30 +8,11 @@ import numpy as np
 import pytest
 
 import ed25519_ref as ref
-from tests_helpers import b
+from tests_helpers import b, lib_ctx, pack, ptr, u8
 
 pytestmark = pytest.mark.gpu
 
 RT_E_INVAL = -1
-
-
-def u8(data, *shape):
-    return np.frombuffer(bytes(data), np.uint8).reshape(*shape).copy()
-
-
-def pack(msgs):
-    lens = np.array([len(m) for m in msgs], np.uint32)
-    offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.uint64)]).astype(np.uint64)
-    return u8(b"".join(msgs) or b"\x00", -1), offs, lens
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-def lib_ctx():
-    from reticulum_amd import _native
-    return _native.load(), _native.context(0)
 
 
 def fixture_cases():
