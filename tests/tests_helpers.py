@@ -121,3 +121,187 @@ def collision_stream(seed, length, dup, sdu=464):
         a, c = dup
         stream[c * sdu:(c + 1) * sdu] = stream[a * sdu:(a + 1) * sdu]
     return bytes(stream)
+
+
+# ---- Resource hashmap edge cases (tests/test_resource_edges.py builds them
+# against the oracle, tests/test_resource_edges_gpu.py runs them on the device)
+
+EDGE_SDU = 8                  # tiny parts: thousands of them cost kilobytes
+EDGE_PARTS = 6000             # 23 whole collision tiles and one of 112 parts
+EDGE_TILE = 256               # COLL_TILE, the collision kernels' workgroup
+EDGE_LDS_GUARD_MAX = 4096     # COLL_LDS_GUARD_MAX: larger guards run k_map_collisions
+EDGE_GUARDS = (1, 2, 224, 255, 256, 257, 600, 4096, 4097, 5000)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_base(seed=7101):
+    """(stream, salt): 6000 parts of 8 bytes, the last one short, whose map
+    hashes under `salt` are all distinct (tests/test_resource_edges.py checks
+    it), so the only repeats in a case are the planted ones."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    stream = rng.integers(0, 256, EDGE_PARTS * EDGE_SDU - 3, dtype=np.uint8).tobytes()
+    return stream, rng.integers(0, 256, 4, dtype=np.uint8).tobytes()
+
+
+def edge_part(i):
+    """Part i of the base stream."""
+    return edge_base()[0][i * EDGE_SDU:(i + 1) * EDGE_SDU]
+
+
+def plant_repeats(stream, pairs, sdu=EDGE_SDU):
+    """`stream` with part a copied over part c for every (a, c) of `pairs`, in
+    order (collision_stream's way, for several pairs).  A copy over a short
+    last part makes that part whole."""
+    s = bytearray(stream)
+    for a, c in pairs:
+        s[c * sdu:(c + 1) * sdu] = s[a * sdu:(a + 1) * sdu]
+    return bytes(s)
+
+
+def sha_map_hashes(parts, salt):
+    """SHA-256(part || salt)[:4] of every part, by hashlib."""
+    import hashlib
+    return b"".join(hashlib.sha256(bytes(p) + bytes(salt)).digest()[:4] for p in parts)
+
+
+def cut(stream, sdu=EDGE_SDU):
+    return [stream[i:i + sdu] for i in range(0, len(stream), sdu)]
+
+
+def edge_later_parts(guard):
+    """The later parts c of the window-edge cases: the first, second and last
+    lane of a tile >= 1 (tile 21), the last part of the launch (lane 111 of
+    the partial tile 23), and the last lane of tile 0 where the guard leaves
+    room for a part guard + 1 before it."""
+    return (5376, 5377, 5631, EDGE_PARTS - 1) + ((EDGE_TILE - 1,) if guard + 1 < EDGE_TILE else ())
+
+
+def edge_cases(guard):
+    """(a, c, expected) for every later part c: a copy of part c - guard sits
+    on the window's oldest place and breaks at c; a copy of part
+    c - guard - 1 is one place too old and is accepted."""
+    out = []
+    for c in edge_later_parts(guard):
+        out += [(c - guard, c, c), (c - guard - 1, c, None)]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def edge_single(guard, a, c):
+    """One case as a single resource over the whole base stream: (stream,
+    salt, map hashes by hashlib, the oracle's first collision of them)."""
+    from oracle import ctoken
+    stream, salt = edge_base()
+    stream = plant_repeats(stream, [(a, c)])
+    hm = sha_map_hashes(cut(stream), salt)
+    return stream, salt, hm, ctoken.first_collision(hm, guard)
+
+
+class Layout:
+    """Parts of several resources for one explicit-form launch: the packed
+    data, each part's offset, length and resource, each resource's first
+    global part index, and per resource the map hashes (hashlib) and the
+    oracle's first collision as the device reports it: start[r] + col, or -1."""
+
+    def __init__(self, resources, salts, guard):
+        from oracle import ctoken
+        self.guard, self.salts = guard, [bytes(s) for s in salts]
+        self.parts = [p for r in resources for p in r]
+        self.res = [r for r, ps in enumerate(resources) for _ in ps]
+        self.len = [len(p) for p in self.parts]
+        self.off = [0] * len(self.parts)
+        for j in range(1, len(self.parts)):
+            self.off[j] = self.off[j - 1] + self.len[j - 1]
+        self.data = b"".join(self.parts)
+        self.start, self.hashes, self.first = [], [], []
+        pos = 0
+        for r, ps in enumerate(resources):
+            hm = sha_map_hashes(ps, self.salts[r])
+            col = ctoken.first_collision(hm, guard)
+            self.start.append(pos)
+            self.hashes.append(hm)
+            self.first.append(-1 if col is None else pos + col)
+            pos += len(ps)
+        self.n_parts, self.n_res = pos, len(resources)
+
+    def mixed_window(self, j):
+        """Does the LDS kernel's window of part j's tile (the tile's parts and
+        the `guard` before them) hold parts of more than one resource?"""
+        j0 = j - j % EDGE_TILE
+        return self.res[max(0, j0 - self.guard)] != self.res[min(j0 + EDGE_TILE, self.n_parts) - 1]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_batched(guard):
+    """The window-edge cases as resources of their own in one launch: (layout,
+    cases) with cases = [(resource, global later part, hit)].  A case resource
+    is parts 0 .. guard + 1 of the base stream and three more, with part
+    guard + 1 overwritten by a copy of part 1 (distance guard: breaks there)
+    or of part 0, the resource's first (guard + 1: accepted).  A filler
+    resource before it moves the later part to the wanted lane of its tile:
+    first, second, last, and lane 100 for the case that ends the launch.
+    Every window so sits in its resource, while the tile's LDS window holds a
+    boundary: behind the later part for lanes 0 and 1, before its window for
+    the others."""
+    _, salt = edge_base()
+    resources, cases, pos = [], [], 0
+    for lane in (0, 1, EDGE_TILE - 1, 100):
+        for hit in (True, False):
+            fill = (lane - (pos + guard + 1)) % EDGE_TILE
+            if fill:
+                resources.append([edge_part(5300 + i) for i in range(fill)])
+            last = lane == 100 and not hit
+            ps = [edge_part(i) for i in range(guard + 2 + (0 if last else 3))]
+            ps[guard + 1] = ps[1 if hit else 0]
+            cases.append((len(resources), pos + fill + guard + 1, hit))
+            resources.append(ps)
+            pos += fill + len(ps)
+    return Layout(resources, [salt] * len(resources), guard), cases
+
+
+# (a, c) repeats in tiles 23, 21 and 22 of one resource, every one inside a
+# window of 224; the earliest later part (5400) is neither planted first nor
+# in the first or last workgroup to run
+SEVERAL = ((5800, 5900), (5390, 5400), (5500, 5640))
+
+
+@functools.lru_cache(maxsize=None)
+def several_two_resources(guard):
+    """Two resources of 3000 parts in one launch.  The first repeats at its
+    parts 2900 and 2600; the second at 2980, 2950 and 2999, all three in the
+    launch's last tile.  Each resource reports its own earliest."""
+    _, salt = edge_base()
+    A = [edge_part(i) for i in range(3000)]
+    B = [edge_part(3000 + i) for i in range(3000)]
+    for ps, pairs in ((A, ((2800, 2900), (2500, 2600))), (B, ((2960, 2980), (2900, 2950), (2990, 2999)))):
+        for a, c in pairs:
+            ps[c] = ps[a]
+    return Layout([A, B], [salt, salt], guard)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_boundaries(guard):
+    """Resource boundaries with equal parts on both sides, all resources under
+    one salt (tests/test_resource_edges.py states what each must give):
+    (layout, names) with names = {name: resource index}.
+      A | B   boundary inside a tile; B's first guard // 2 + 1 parts copy A's last
+      C | D   the same with the boundary on a tile boundary
+      one * 300   one-part resources of identical content
+      E | F   F starts inside a tile with a copy of E's last part, and its part
+              `guard` repeats its own first part
+    """
+    _, salt = edge_base()
+    pool = iter(range(EDGE_PARTS - 1))
+    fresh = lambda n: [edge_part(next(pool)) for _ in range(n)]
+    half = guard // 2 + 1
+    A = fresh(guard + 50)
+    B = A[-half:] + fresh(guard + 50 - half)
+    C = fresh(guard + EDGE_TILE - (2 * (guard + 50) + guard) % EDGE_TILE)
+    D = C[-half:] + fresh(guard + 50 - half)
+    ones = [fresh(1)] * 300
+    E = fresh(100)
+    F = [E[-1]] + fresh(guard + 9)
+    F[guard] = F[0]
+    resources = [A, B, C, D] + ones + [E, F]
+    names = {"A": 0, "B": 1, "C": 2, "D": 3, "ones": range(4, 304), "E": 304, "F": 305}
+    return Layout(resources, [salt] * len(resources), guard), names
