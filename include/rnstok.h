@@ -25,6 +25,7 @@
  *   rt_hdlc_deframe_slots  the same, each frame in a 128-B-aligned slot
  *   rt_ifac_mask       IFAC on transmit          RNS/Transport.py:1069-1101
  *   rt_ifac_unmask     IFAC on inbound           RNS/Transport.py:1441-1475
+ *   rt_ifac_sign/check the IFAC's signature      RNS/Transport.py:1073, 1470-1474
  *   rt_packet_unpack   Packet.unpack + get_hash  RNS/Packet.py:236-268, 342-353
  *   rt_packet_pack_headers  Packet.pack header   RNS/Packet.py:167-228
  *   rt_frames_compact  frames a read hands on    RNS/Interfaces/TCPInterface.py:391-401
@@ -461,8 +462,8 @@ int rt_frames_compact(rt_ctx *ctx, const uint64_t *frame_off, const uint32_t *fr
                       int64_t *frame_pair, int64_t *n_frames, void *workspace, void *stream);
 /* IFAC on transmit: packet i (pkt + pkt_off[i], pkt_len[i] >= 2 bytes) with
  * its access code ifac + i*ifac_size (the last ifac_size bytes of the
- * interface identity's Ed25519 signature of the packet, computed by the
- * caller; signing stays on the host) becomes pkt_len[i] + ifac_size bytes at
+ * interface identity's Ed25519 signature of the packet: rt_ifac_sign makes it
+ * on the device, or the caller supplies its own) becomes pkt_len[i] + ifac_size bytes at
  * out + out_off[i]: IFAC flag set, IFAC inserted after the 2 header bytes,
  * all but the IFAC masked with HKDF(len + ifac_size, ifac, ifac_key).
  * ifac_key: key_len (<= 64) bytes shared by the batch.  DEVICE pointers. */
@@ -475,11 +476,39 @@ int rt_ifac_mask(rt_ctx *ctx, const uint8_t *pkt, const uint64_t *pkt_off, const
  * cleared) to out + out_off[i].  status 1: the reference drops the packet
  * before signing.  out_len (may be NULL) receives the unmasked length,
  * pkt_len[i] - ifac_size, where status[i] is 0 and 0 elsewhere, ready as
- * rt_packet_unpack's pkt_len.  The caller then compares ifac with the tail of
- * sign(unmasked packet) (Transport.py:1477-1481). */
+ * rt_packet_unpack's pkt_len.  The access code is then compared with the tail
+ * of sign(unmasked packet) (Transport.py:1470-1474): rt_ifac_check does that
+ * on the device over (out, out_off, out_len, ifac_out, status). */
+#define RT_IFAC_OK       0   /* unmasked (and, after rt_ifac_check, the access code matches) */
+#define RT_IFAC_DROPPED  1   /* no IFAC flag, or not longer than 2 + ifac_size */
+#define RT_IFAC_MISMATCH 2   /* rt_ifac_check: access code does not match */
 int rt_ifac_unmask(rt_ctx *ctx, const uint8_t *pkt, const uint64_t *pkt_off, const uint32_t *pkt_len,
                    uint32_t ifac_size, const uint8_t *ifac_key, uint32_t key_len, uint8_t *ifac_out, uint8_t *out,
                    const uint64_t *out_off, int32_t *status, uint32_t *out_len, uint32_t n, void *stream);
+/* The access code of an interface with IFAC, made and checked on the device:
+ * ifac = sign(packet)[-ifac_size:] with the interface identity's Ed25519 key
+ * (Transport.transmit, Transport.py:1073; Transport.inbound's
+ * expected_ifac, Transport.py:1470-1474).  One 32-byte seed (ifac_key[32:64]
+ * of Identity.from_bytes(ifac_key), Reticulum.py:968-971) and its 32-byte
+ * public key (rt_ed25519_public of the seed; trusted) serve the whole batch;
+ * packet i is pkt + pkt_off[i], pkt_len[i] bytes at any alignment, and an item
+ * with pkt_len[i] == 0 is skipped without its offset being used.  The
+ * signature is rt_ed25519_sign's (the reference's internal provider), with the
+ * fixed-base multiplication from a table of [2^i]B; constant time in the seed
+ * as rt_ed25519_sign is.  ifac_size is 1..64 (above 32 the code reaches into
+ * R).  DEVICE pointers, enqueued on the stream.
+ *   rt_ifac_sign   writes the code to ifac_out + i*ifac_size (zeros for a
+ *                  skipped item), ready as rt_ifac_mask's ifac.
+ *   rt_ifac_check  where status[i] == RT_IFAC_OK and the code differs from
+ *                  ifac + i*ifac_size: status[i] = RT_IFAC_MISMATCH and
+ *                  pkt_len[i] = 0, so that rt_packet_unpack and everything
+ *                  after it drop the packet as the reference's `return` does.
+ *                  Items with another status keep status and length. */
+int rt_ifac_sign(rt_ctx *ctx, const uint8_t *seed, const uint8_t *pub, const uint8_t *pkt, const uint64_t *pkt_off,
+                 const uint32_t *pkt_len, uint8_t *ifac_out, uint32_t ifac_size, uint32_t n, void *stream);
+int rt_ifac_check(rt_ctx *ctx, const uint8_t *seed, const uint8_t *pub, const uint8_t *pkt, const uint64_t *pkt_off,
+                  uint32_t *pkt_len, const uint8_t *ifac, uint32_t ifac_size, int32_t *status, uint32_t n,
+                  void *stream);
 /* Packet.unpack + get_hash per packet (96 bytes).  ok = 0 where unpack
  * returns False (hop count >= 128, packet too short for its header). */
 typedef struct rt_packet_fields {

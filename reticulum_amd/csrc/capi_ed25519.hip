@@ -47,6 +47,18 @@ int public_check(rt_ctx *c, const uint8_t *seeds, uint64_t seed_stride, const ui
     return RT_OK;
 }
 
+int ifac_sign_check(const char *fn, rt_ctx *c, const uint8_t *seed, const uint8_t *pub, const uint8_t *pkt,
+                    const uint64_t *pkt_off, const uint32_t *pkt_len, const uint8_t *ifac, uint32_t ifac_size,
+                    uint32_t n) {
+    if (!c) return fail(RT_E_INVAL, "null context");
+    if (ifac_size < 1 || ifac_size > 64) return fail(RT_E_INVAL, std::string(fn) + ": ifac_size outside 1..64");
+    if (n == 0) return RT_OK;
+    if (!seed || !pub) return fail(RT_E_INVAL, std::string(fn) + ": null seed or public key");
+    if (!pkt || !pkt_off || !pkt_len) return fail(RT_E_INVAL, std::string(fn) + ": null packets, offsets or lengths");
+    if (!ifac) return fail(RT_E_INVAL, std::string(fn) + ": null access codes");
+    return RT_OK;
+}
+
 // The messages of a host call: the bytes [0, extent) of msgs that the n spans
 // cover, with their offsets and lengths, staged next to each other.
 struct HostMsgs {
@@ -170,6 +182,28 @@ int rt_ed25519_public_host(rt_ctx *c, const uint8_t *seeds, uint64_t seed_stride
     RT_HIP(launch_ed25519_public(a, hc.stream()), "ed25519 public launch");
     hc.get_rows(out, out_stride < 32 ? 32 : out_stride, o_out, 32, n, "D2H public keys");
     return hc.finish();
+}
+
+int rt_ifac_sign(rt_ctx *c, const uint8_t *seed, const uint8_t *pub, const uint8_t *pkt, const uint64_t *pkt_off,
+                 const uint32_t *pkt_len, uint8_t *ifac_out, uint32_t ifac_size, uint32_t n, void *stream) {
+    int rc = ifac_sign_check("rt_ifac_sign", c, seed, pub, pkt, pkt_off, pkt_len, ifac_out, ifac_size, n);
+    if (rc || n == 0) return rc;
+    RT_HIP(hipSetDevice(c->device), "hipSetDevice");
+    const IfacSignArgs a{seed, pub, 0, pkt, pkt_off, pkt_len, ifac_size, ifac_out, nullptr, nullptr, nullptr, n};
+    RT_HIP(launch_ifac_sign(a, as_stream(stream)), "ifac sign launch");
+    return RT_OK;
+}
+
+int rt_ifac_check(rt_ctx *c, const uint8_t *seed, const uint8_t *pub, const uint8_t *pkt, const uint64_t *pkt_off,
+                  uint32_t *pkt_len, const uint8_t *ifac, uint32_t ifac_size, int32_t *status, uint32_t n,
+                  void *stream) {
+    int rc = ifac_sign_check("rt_ifac_check", c, seed, pub, pkt, pkt_off, pkt_len, ifac, ifac_size, n);
+    if (rc || n == 0) return rc;
+    if (!status) return fail(RT_E_INVAL, "rt_ifac_check: null status");
+    RT_HIP(hipSetDevice(c->device), "hipSetDevice");
+    const IfacSignArgs a{seed, pub, 0, pkt, pkt_off, pkt_len, ifac_size, nullptr, ifac, status, pkt_len, n};
+    RT_HIP(launch_ifac_sign(a, as_stream(stream)), "ifac check launch");
+    return RT_OK;
 }
 
 }  // extern "C"

@@ -2,8 +2,8 @@
 // (RNS/Cryptography/pure25519/eddsa.py, basic.py): SHA-512, arithmetic mod the
 // group order L, Edwards points in extended coordinates over the field of
 // x25519_device.h, and verify / sign / public key on top of them.  Device code
-// and plain host C++ (tests/ed25519_host/ed_check.cpp compiles it with g++ and
-// sanitizers).  No HIP builtins, no inline assembly.
+// and plain host C++ (tests/ed25519_host/ed_check.cpp and table_check.cpp
+// compile it with g++ and sanitizers).  No HIP builtins, no inline assembly.
 //
 // Field elements keep x25519_device.h's three limb bounds (carried, one add,
 // products); every function here says what it takes and returns, and nothing
@@ -12,12 +12,15 @@
 // Signing and public keys are constant time by construction: no branch, loop
 // bound or address depends on the seed, a, r or anything derived from them;
 // the fixed-base multiplication adds B or the identity, chosen by a mask, in
-// every step.  Verification handles public data only and still runs one
+// every step.  The table form (ge_scalarmult_base_table) adds entry i of the
+// table of [2^i]B or the identity in step i, again by mask: the table is
+// indexed by the loop counter alone, never by the scalar.  Verification handles public data only and still runs one
 // instruction stream per item: every item computes every stage and the stages'
 // verdicts are combined at the end; only the number of SHA-512 blocks depends
 // on the item (its message length).
 #pragma once
 #include "x25519_device.h"
+#include "ed25519_base_table.h"
 
 namespace rnstok {
 
@@ -557,6 +560,34 @@ X25519_FN void ge_scalarmult_base(ge &q, const uint32_t e_in[8]) {
     }
 }
 
+// q = [e]B for e < 2^253, without doublings: step i = 0..252 adds entry i of
+// the table of [2^i]B (ed25519_base_table.h) or the identity (1, 1, 0), chosen
+// by mask from bit i of e.  The additions are complete, so the order of the
+// steps does not matter and the sum may pass through any point.  The table
+// index is the loop counter: the same loads and instructions whatever e is.
+X25519_FN void ge_scalarmult_base_table(ge &q, const uint32_t e_in[8]) {
+    uint32_t e[8];
+    X25519_UNROLL
+    for (int k = 0; k < 8; ++k) e[k] = e_in[k];
+    ge_identity(q);
+    X25519_NO_UNROLL
+    for (int t = 0; t < ED25519_BASE_TABLE_ENTRIES; ++t) {
+        const uint32_t m = 0u - (e[0] & 1u);
+        X25519_UNROLL
+        for (int k = 0; k < 7; ++k) e[k] = (e[k] >> 1) | (e[k + 1] << 31);
+        e[7] >>= 1;
+        fe ymx, ypx, t2d;
+        X25519_UNROLL
+        for (int i = 0; i < 10; ++i) {
+            const uint32_t id = i == 0 ? 1u : 0u;
+            ymx.v[i] = id ^ (m & (id ^ ED25519_BASE_TABLE[t][0][i]));
+            ypx.v[i] = id ^ (m & (id ^ ED25519_BASE_TABLE[t][1][i]));
+            t2d.v[i] = m & ED25519_BASE_TABLE[t][2][i];
+        }
+        ge_add_cached_z1(q, q, ymx, ypx, t2d);
+    }
+}
+
 // q = [s]B + [h]nA for s, h < 2^253 (reduced mod L), nA = -A and bma = B - A:
 // 253 steps of a doubling and the addition of one of B, -A, B - A or the
 // identity, chosen by mask from the two scalars' bits.
@@ -729,6 +760,34 @@ X25519_FN void ed25519_sign_words(uint32_t sig[16], const uint8_t *seed_bytes, c
     }
     ge_scalarmult_base(q, r);      // r < L < 2^253
     ge_encode(sig, q);
+    ed_hint(h, sig, pk, msg, len);
+    load_words(seed, seed_bytes);
+    ed_expand_seed(a, prefix, seed);
+    sc_muladd(sig + 8, r, h, a);
+}
+
+// The interface access code's signature (Transport.py:1073, :1470-1474):
+// eddsa.py signature as ed25519_sign_words computes it, for a batch that shares
+// one seed and its public key (pk_bytes, trusted), with [r]B from the table of
+// [2^i]B: r < L < 2^253.  The seed is expanded once for the prefix and once
+// more for a, so that neither is held across the multiplication.
+X25519_FN void ifac_sign_words(uint32_t sig[16], const uint8_t *seed_bytes, const uint8_t *pk_bytes,
+                               const uint8_t *msg, uint32_t len) {
+    uint32_t seed[8], a[8], r[8], pk[8], h[8];
+    uint64_t prefix[4];
+    ge q;
+    load_words(seed, seed_bytes);
+    ed_expand_seed(a, prefix, seed);
+    {
+        uint64_t st[8];
+        sha512_head_msg<4>(st, prefix, msg, len);
+        uint32_t d[16];
+        sha512_le_words(d, st);
+        sc_reduce<16>(r, d);
+    }
+    ge_scalarmult_base_table(q, r);
+    ge_encode(sig, q);
+    load_words(pk, pk_bytes);
     ed_hint(h, sig, pk, msg, len);
     load_words(seed, seed_bytes);
     ed_expand_seed(a, prefix, seed);

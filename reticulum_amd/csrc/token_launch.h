@@ -133,6 +133,31 @@ hipError_t launch_ed25519_verify(const Ed25519VerifyArgs &a, hipStream_t s);
 hipError_t launch_ed25519_sign(const Ed25519SignArgs &a, hipStream_t s);
 hipError_t launch_ed25519_public(const Ed25519PublicArgs &a, hipStream_t s);
 
+// The interface access code (k_ifac_sign): item i's packet is pkt + pkt_off[i]
+// (pkt_len[i] bytes, any alignment; an item of length 0 is skipped and its
+// offset never used), signed with the batch's one seed and public key; the
+// code is the last ifac_size (1..64) bytes of the signature.  status null:
+// make, the code goes to ifac_out + i*ifac_size (zeros for a skipped item).
+// status given: check, the code is compared with ifac_in + i*ifac_size where
+// status[i] is 0, and a mismatch sets status[i] = IFAC_MISMATCH and
+// pkt_len_io[i] (the same array as pkt_len) = 0.
+constexpr int32_t IFAC_MISMATCH = 2;       // RT_IFAC_MISMATCH (include/rnstok.h)
+struct IfacSignArgs {
+    const uint8_t *seed;           // 32 bytes
+    const uint8_t *pub;            // 32 bytes
+    uint64_t key_stride;           // 0: one seed and one key for the batch (see k_ifac_sign)
+    const uint8_t *pkt;
+    const uint64_t *pkt_off;
+    const uint32_t *pkt_len;
+    uint32_t ifac_size;
+    uint8_t *ifac_out;             // make
+    const uint8_t *ifac_in;        // check
+    int32_t *status;               // check, else null
+    uint32_t *pkt_len_io;          // check: pkt_len, writable
+    uint32_t n;
+};
+hipError_t launch_ifac_sign(const IfacSignArgs &a, hipStream_t s);
+
 // Resource map hashes (resource_kernels.hip): part j = data + part_off[j]
 // (part_len[j] bytes), or with part_off null the uniform segmentation
 // data[j*sdu, min((j+1)*sdu, size)); salt = salts + part_res[j]*salt_len.

@@ -685,6 +685,50 @@ def ifac_unmask(pkt, pkt_off, pkt_len, ifac_key, ifac_out, out, out_off, status,
                                      _p(out_len), n, _stream(stream, pkt.device)))
 
 
+IFAC_OK, IFAC_DROPPED, IFAC_MISMATCH = 0, 1, 2      # RT_IFAC_* (include/rnstok.h)
+
+
+def _ifac_sign_args(seed, public_key, pkt, pkt_off, pkt_len, ifac):
+    _check_u8(seed, public_key, pkt, ifac)
+    if seed.numel() != 32 or public_key.numel() != 32:
+        raise ValueError("seed and public_key are 32 bytes each")
+    n = pkt_off.numel()
+    _check_i64(n, pkt_off=pkt_off)
+    _check_i32(n, pkt_len=pkt_len)
+    if ifac.dim() != 2 or ifac.shape[0] != n or not 1 <= ifac.shape[1] <= 64:
+        raise ValueError(f"access codes must be an ({n}, 1..64) uint8 matrix")
+    return n
+
+
+def ifac_sign(seed, public_key, pkt, pkt_off, pkt_len, ifac_out, stream=None):
+    """The access code Transport.transmit makes (Transport.py:1073):
+    ifac_out[i] ((n, ifac_size) uint8, ifac_size 1..64) = the last ifac_size
+    bytes of the signature of packet i (pkt[pkt_off[i]:][:pkt_len[i]]) under
+    the interface identity's 32-byte ``seed`` (ifac_key[32:64]) and its
+    ``public_key`` (ed25519_public of the seed).  A packet of length 0 is
+    skipped (its offset is never used) and its row zeroed."""
+    n = _ifac_sign_args(seed, public_key, pkt, pkt_off, pkt_len, ifac_out)
+    lib = _native.load()
+    _native.check(lib.rt_ifac_sign(_ctx_of(pkt), _p(seed), _p(public_key), _p(pkt), _p(pkt_off), _p(pkt_len),
+                                   _p(ifac_out), ifac_out.shape[1], n, _stream(stream, pkt.device)))
+
+
+def ifac_check(seed, public_key, pkt, pkt_off, pkt_len, ifac, status, stream=None):
+    """Transport.inbound's access-code check (Transport.py:1470-1474) after
+    ifac_unmask: where status[i] is IFAC_OK and ifac[i] ((n, ifac_size)) is
+    not the tail of the signature of packet i, status[i] becomes
+    IFAC_MISMATCH and pkt_len[i] 0 (so unpack and the token stages drop the
+    packet, the reference's ``return``).  Entries with another status, or of
+    length 0, are left as they are."""
+    n = _ifac_sign_args(seed, public_key, pkt, pkt_off, pkt_len, ifac)
+    _check_i32(n, status=status)
+    if status is None:
+        raise ValueError("status is required")
+    lib = _native.load()
+    _native.check(lib.rt_ifac_check(_ctx_of(pkt), _p(seed), _p(public_key), _p(pkt), _p(pkt_off), _p(pkt_len),
+                                    _p(ifac), ifac.shape[1], _p(status), n, _stream(stream, pkt.device)))
+
+
 def packet_unpack(pkt, pkt_off, pkt_len, fields, stream=None):
     """Packet.unpack + get_hash (Packet.py:242-275, 342-353): fields (n, 96)
     uint8 receives one rt_packet_fields record per packet

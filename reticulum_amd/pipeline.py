@@ -5,13 +5,15 @@ for a true end-to-end node pipeline").
 Outbound, as a node sends DATA packets through an interface with IFAC:
     Token.encrypt            Token.py:87-97 (Packet.pack -> Destination/Link.encrypt)
     Packet.pack header       Packet.py:178-228
-    IFAC mask                Transport.py:1069-1101 (transmit)
+    IFAC sign                Transport.py:1073 (with ifac_size; else the
+                             caller supplies the access codes)
+    IFAC mask                Transport.py:1075-1101 (transmit)
     HDLC framing             TCPInterface.py:44-53, 323 (process_outgoing)
 Inbound, as the interface's read loop hands frames to Transport:
     HDLC deframing           TCPInterface.py:387-410 (read_loop)
-    IFAC unmask              Transport.py:1441-1475 (inbound; the Ed25519
-                             signature check that follows, :1477-1481, stays
-                             with the caller: `ifac` is returned for it)
+    IFAC unmask              Transport.py:1441-1468 (inbound)
+    IFAC check               Transport.py:1470-1474 (with check_ifac; else
+                             `ifac` is returned for the caller's own check)
     Packet.unpack + hash     Packet.py:242-275, 342-353
     Token.decrypt            Token.py:100-114 (Link/Identity.decrypt)
 
@@ -42,14 +44,39 @@ FRAME_OK = 0                # RT_FRAME_OK (include/rnstok.h)
 CT_PHASE = HEADER_1_LEN + 16
 
 
-def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac, ifac_key, flags=None, hops=None, stream=None,
-             aligned=True):
+_ifac_public = {}          # (device index, seed bytes) -> the seed's public key on that device
+
+
+def ifac_identity(ifac_key):
+    """(seed, public key) of the interface identity Reticulum builds from a
+    64-byte ``ifac_key`` (device uint8): Identity.from_bytes(ifac_key)
+    (Reticulum.py:968-971) signs with ifac_key[32:64].  The public key is
+    computed once per key and device (device.ed25519_public) and kept; looking
+    it up reads the key back to the host."""
+    if ifac_key.numel() != 64:
+        raise ValueError("the access code is signed with a 64-byte ifac_key (Identity.from_bytes)")
+    seed = ifac_key[32:64]
+    tag = (ifac_key.device.index, bytes(seed.tolist()))
+    pub = _ifac_public.get(tag)
+    if pub is None:
+        pub = torch.empty((1, 32), dtype=torch.uint8, device=ifac_key.device)
+        device.ed25519_public(seed.view(1, 32), pub)
+        torch.cuda.current_stream(ifac_key.device).synchronize()
+        _ifac_public[tag] = pub
+    return seed, pub
+
+
+def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=None, flags=None, hops=None,
+             stream=None, aligned=True, ifac_size=None):
     """n DATA packets of one length L, one link key: pt (n, L) uint8, iv (n,
     16), destination_hash (n, 16), context (n,) uint8, flags/hops (n,) uint8
     (default 0: HEADER_1 DATA, hop 0), ifac (n, ifac_size) the access codes
     (the tail of the interface identity's signature of each packet, made by
     the caller; None or zero columns: an interface without IFAC, no mask),
-    ifac_key (K,) uint8 (unused without IFAC).  Returns (stream, frame_off): the HDLC
+    ifac_key (K,) uint8 (unused without IFAC).  With ``ifac`` None and
+    ``ifac_size`` (1..64) given the codes are made on the device instead
+    (device.ifac_sign between pack and mask, Transport.py:1073), signed with
+    ifac_key[32:64] of a 64-byte ifac_key.  Returns (stream, frame_off): the HDLC
     byte stream is stream[:frame_off[n]] (int64 on the device), frame i at
     stream[frame_off[i]:frame_off[i+1]].  ``aligned`` (default) builds the
     packets in 128-B-aligned slots (token ciphertext on a line); False packs
@@ -60,7 +87,10 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac, ifac_key, flag
         flags = flags if flags is not None else torch.zeros(n, dtype=torch.uint8, device=dev)
         hops = hops if hops is not None else torch.zeros(n, dtype=torch.uint8, device=dev)
         pl = HEADER_1_LEN + token_len(L)
-        isz = ifac.shape[1] if ifac is not None else 0
+        sign = ifac is None and bool(ifac_size)
+        if sign:
+            seed, pub = ifac_identity(ifac_key)
+        isz = ifac_size if sign else ifac.shape[1] if ifac is not None else 0
         if aligned:
             raw = device.aligned_rows(n, pl, CT_PHASE, dev)
             stride = raw.stride(0)
@@ -76,8 +106,11 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac, ifac_key, flag
             ml = pl + isz
             masked = torch.empty(n * ml, dtype=torch.uint8, device=dev)
             m_off = torch.arange(n, dtype=torch.int64, device=dev) * ml
-            device.ifac_mask(flat, off, torch.full((n,), pl, dtype=torch.int32, device=dev), ifac, ifac_key, masked,
-                             m_off, stream=stream)
+            p_len = torch.full((n,), pl, dtype=torch.int32, device=dev)
+            if sign:
+                ifac = torch.empty((n, isz), dtype=torch.uint8, device=dev)
+                device.ifac_sign(seed, pub, flat, off, p_len, ifac, stream=stream)
+            device.ifac_mask(flat, off, p_len, ifac, ifac_key, masked, m_off, stream=stream)
         else:
             # an interface without IFAC transmits the packet as packed
             # (Transport.py:1069-1071: the mask applies only with ifac_identity)
@@ -89,7 +122,8 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac, ifac_key, flag
     return framed, frame_off
 
 
-def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None):
+def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
+            check_ifac=False):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -105,7 +139,9 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     into the first ``n_frames`` (a device scalar) entries of the per-frame
     arrays, whose remaining entries are empty: ``frame_pair`` (their pair
     index), ``ifac_status`` (0: unmasked; 1: dropped before the signature
-    check), ``ifac`` (the access code for the caller's signature check),
+    check; 2, with ``check_ifac`` only: the access code does not match),
+    ``ifac`` (the access code, for the caller's signature check where
+    ``check_ifac`` is off),
     ``fields`` (rt_packet_fields; ok = 0 where unpack fails), and the token's
     outcome: ``status`` (RT_* token status; TOO_SHORT where there is no
     packet) with the plaintext at ``pt[pt_off[i]: pt_off[i] + pt_len[i]]``.
@@ -119,9 +155,18 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     −8 % for the path, mostly the unmask reading slotted frames).  The default
     (None) takes slots when their padding is at most the stream's own size
     (a Reticulum stream has about two pairs per packet; a max_pairs sized for
-    a stream of nothing but flags would multiply the buffers instead)."""
+    a stream of nothing but flags would multiply the buffers instead).
+
+    ``check_ifac`` (with ``ifac_size`` > 0 and a 64-byte ``ifac_key``) runs
+    the reference's access-code check on the device (device.ifac_check after
+    the unmask, Transport.py:1470-1474): a packet whose code is not the tail
+    of the interface identity's signature of it gets ``ifac_status`` 2 and is
+    dropped there, as the reference returns: unpack reports ok = 0, its token
+    status is TOO_SHORT and nothing of it is decrypted."""
     if aligned is None:
         aligned = device.LINE * (max_pairs + 1) <= buf.numel()
+    if check_ifac and ifac_size:
+        seed, pub = ifac_identity(ifac_key)
     with _on(stream):      # temporaries allocated on the stream that uses them
         dev = buf.device
         # (at least one byte: an empty read still gives every later stage a
@@ -151,6 +196,8 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
             un = torch.empty_like(out)
             device.ifac_unmask(out, f_off, f_len, ifac_key, ifac, un, f_off, ifac_status, out_len=p_len,
                                stream=stream)
+            if check_ifac:
+                device.ifac_check(seed, pub, un, f_off, p_len, ifac, ifac_status, stream=stream)
         else:
             # no IFAC on the interface: a packet with the IFAC flag set is
             # dropped, the others go to unpack as they are

@@ -3,7 +3,9 @@
 * ``HDLC.escape`` / ``hdlc_frame_batch``   TCPInterface.py:44-53, :323
 * ``Deframer``                              the HDLC read loop, TCPInterface.py:387-410, :336-339
 * ``ifac_mask_batch`` / ``ifac_unmask_batch``  Transport.py:1069-1101 / :1441-1475
-  (the Ed25519 signature that yields the IFAC stays with the caller)
+  (with access codes the caller supplies or checks)
+* ``transmit_batch`` / ``receive_batch``    the same with the access code signed and
+  checked on the device, Transport.py:1073 / :1470-1474
 * ``unpack_batch``                          Packet.unpack + get_hash, Packet.py:236-268, 342-353
 * ``pack_headers_batch``                    Packet.pack's header, Packet.py:167-228
 
@@ -251,6 +253,80 @@ def ifac_unmask_batch(raws, ifac_size, ifac_key, device=None):
             o = int(out_off[i])
             res.append((ifac[i * ifac_size:(i + 1) * ifac_size], out[o:o + int(lens[i]) - ifac_size]))
     return res
+
+
+def _ifac_identity(d, ifac_key):
+    """Device pointers to the seed and the public key of the interface
+    identity, Identity.from_bytes(ifac_key) (Reticulum.py:968-971): it signs
+    with ifac_key[32:64]."""
+    p_seed = d.up(np.frombuffer(bytes(ifac_key)[32:], np.uint8))
+    p_pub = d.alloc(32)
+    _native.check(d.lib.rt_ed25519_public(d.ctx, p_seed, 0, p_pub, 32, 1, None))
+    return p_seed, p_pub
+
+
+def _check_ifac_size(ifac_size, ifac_key):
+    if not 1 <= int(ifac_size) <= 64:
+        raise ValueError("ifac_size must be 1..64")
+    if len(bytes(ifac_key)) != 64:
+        raise ValueError("the access code is signed with a 64-byte ifac_key (Identity.from_bytes)")
+    return int(ifac_size)
+
+
+def transmit_batch(raws, ifac_size, ifac_key, device=None):
+    """Transport.transmit up to process_outgoing (Transport.py:1069-1102) for
+    many packets on an interface with IFAC: each access code is signed on the
+    device (sign(raw)[-ifac_size:] under Identity.from_bytes(ifac_key)), then
+    the packet is masked.  Returns the masked packets."""
+    n = len(raws)
+    size = _check_ifac_size(ifac_size, ifac_key)
+    if n == 0:
+        return []
+    if any(len(r) < 2 for r in raws):
+        raise ValueError("packets need the 2 header bytes")
+    buf, off, lens = _pack(raws)
+    out_len = lens.astype(np.uint64) + size
+    out_off = np.zeros(n, np.uint64)
+    out_off[1:] = np.cumsum(out_len[:-1])
+    key = np.frombuffer(bytes(ifac_key), np.uint8)
+    with _Dev(device) as d:
+        p_seed, p_pub = _ifac_identity(d, ifac_key)
+        p_buf, p_off, p_len = d.up(buf), d.up(off), d.up(lens)
+        p_ifac = d.alloc(n * size)
+        p_out = d.alloc(int(out_len.sum()))
+        _native.check(d.lib.rt_ifac_sign(d.ctx, p_seed, p_pub, p_buf, p_off, p_len, p_ifac, size, n, None))
+        _native.check(d.lib.rt_ifac_mask(d.ctx, p_buf, p_off, p_len, p_ifac, size, d.up(key), len(key), p_out,
+                                         d.up(out_off), n, None))
+        out = d.down(p_out, np.zeros(int(out_len.sum()), np.uint8)).tobytes()
+    return [out[int(o):int(o) + int(l)] for o, l in zip(out_off, out_len)]
+
+
+def receive_batch(raws, ifac_size, ifac_key, device=None):
+    """Transport.inbound's IFAC block (Transport.py:1441-1480) for many
+    received packets on an interface with IFAC: the reassembled packet that
+    goes on to Packet.unpack, or None where the reference returns early (no
+    IFAC flag, not longer than 2 + ifac_size, or an access code that is not
+    the tail of the identity's signature of the reassembled packet)."""
+    n = len(raws)
+    size = _check_ifac_size(ifac_size, ifac_key)
+    if n == 0:
+        return []
+    buf, off, lens = _pack(raws)
+    key = np.frombuffer(bytes(ifac_key), np.uint8)
+    with _Dev(device) as d:
+        p_seed, p_pub = _ifac_identity(d, ifac_key)
+        p_out = d.alloc(max(int(lens.sum()), 1))
+        p_ifac = d.alloc(n * size)
+        p_st = d.alloc(4 * n)
+        p_len = d.alloc(4 * n)
+        p_off = d.up(off)
+        _native.check(d.lib.rt_ifac_unmask(d.ctx, d.up(buf), p_off, d.up(lens), size, d.up(key), len(key), p_ifac,
+                                           p_out, p_off, p_st, p_len, n, None))
+        _native.check(d.lib.rt_ifac_check(d.ctx, p_seed, p_pub, p_out, p_off, p_len, p_ifac, size, p_st, n, None))
+        st = d.down(p_st, np.zeros(n, np.int32))
+        ln = d.down(p_len, np.zeros(n, np.uint32))
+        out = d.down(p_out, np.zeros(max(int(lens.sum()), 1), np.uint8)).tobytes()
+    return [out[int(off[i]):int(off[i]) + int(ln[i])] if st[i] == 0 else None for i in range(n)]
 
 
 # ---------------------------------------------------------------- packets --
