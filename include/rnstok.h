@@ -31,6 +31,8 @@
  *   rt_frames_compact  frames a read hands on    RNS/Interfaces/TCPInterface.py:391-401
  *                      (one process_incoming call per frame, in stream order)
  *   rt_token_spans     packet.data (the token)   RNS/Packet.py:262-275 (data after the header)
+ *   rt_linktable_* /   the link of a DATA packet  RNS/Transport.py:2161-2176 (first link in
+ *   rt_link_spans      and whether it is decrypted  active_links with the link_id), RNS/Link.py:941-1148
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
@@ -536,6 +538,83 @@ int rt_token_spans(rt_ctx *ctx, const rt_packet_fields *fields, const uint64_t *
 int rt_packet_pack_headers(rt_ctx *ctx, const uint8_t *flags, const uint8_t *hops, const uint8_t *transport_id,
                            const uint8_t *destination_hash, const uint8_t *context, uint8_t *out,
                            const uint64_t *out_off, uint32_t n, void *stream);
+
+/* ---- link table and dispatch (Transport.py:2161-2176, Link.py:941-1148) -- */
+/* A node has many links at once.  Transport.inbound finds the link of a DATA
+ * packet as the first link in active_links whose link_id equals the packet's
+ * destination hash; a link table does that on the device: 16-byte link id ->
+ * a uint32 value of the caller's (the index of the link's key in its key set).
+ * It is an open-addressing hash table in device memory with a fixed number of
+ * slots, the smallest power of two that is at least 2 * max_links
+ * (rt_linktable_capacity); max_links is 1 .. 2^29.  No id value is special.
+ *
+ * The calls below take DEVICE pointers and a stream and only enqueue; ids are
+ * n x 16 bytes at any alignment; n == 0 is RT_OK, n is at most 2^30 - 2.  The
+ * _host forms take HOST pointers and return when the outputs are filled.
+ * Calls on one table take effect in the order the host makes them, whatever
+ * their streams: a call on another stream than the one before it first waits
+ * for that one.  rt_linktable_destroy never blocks: the memory is released
+ * once the last call has completed (the key sets' rule, above).
+ *
+ * rt_linktable_insert writes status[i]:
+ *   RT_LINK_OK         entered with values[i];
+ *   RT_LINK_DUPLICATE  the id is already present, or appears at a lower index
+ *                      of this batch: the earlier one stays, as the first
+ *                      match in active_links wins.  Within a batch the lowest
+ *                      index wins whatever the scheduling;
+ *   RT_LINK_FULL       no free slot.  A table that holds at most max_links
+ *                      entries never gives it.  When the new ids of one batch
+ *                      outnumber the free slots, which of them get the last
+ *                      slots is not specified.
+ * rt_linktable_remove writes RT_LINK_OK, or RT_LINK_MISSING where the id is not
+ * present or is removed at a lower index of this batch.  Ids further along the
+ * probe chain are still found, and the id can be inserted again.  The slots
+ * removals leave behind are reclaimed by a rebuild in place, enqueued ahead of
+ * an insert when removals came since the last rebuild and the host's upper
+ * bound on used slots plus n passes 3/4 of the capacity.
+ * rt_linktable_lookup writes values_out[i] (0xFFFFFFFF on a miss) and
+ * found_out[i] (1 / 0).  rt_linktable_count copies the number of entries
+ * present to *count_out (DEVICE) on the stream.  Every probe is bounded by the
+ * capacity. */
+#define RT_LINK_OK        0
+#define RT_LINK_DUPLICATE 1
+#define RT_LINK_FULL      2
+#define RT_LINK_MISSING   3
+typedef struct rt_linktable rt_linktable;
+rt_linktable *rt_linktable_create(rt_ctx *ctx, uint32_t max_links);
+void          rt_linktable_destroy(rt_linktable *tab);
+uint32_t      rt_linktable_capacity(const rt_linktable *tab);
+int rt_linktable_insert(rt_linktable *tab, const uint8_t *ids, const uint32_t *values, int32_t *status, uint32_t n,
+                        void *stream);
+int rt_linktable_remove(rt_linktable *tab, const uint8_t *ids, int32_t *status, uint32_t n, void *stream);
+int rt_linktable_lookup(rt_linktable *tab, const uint8_t *ids, uint32_t *values_out, uint8_t *found_out, uint32_t n,
+                        void *stream);
+int rt_linktable_count(rt_linktable *tab, uint32_t *count_out, void *stream);
+int rt_linktable_insert_host(rt_linktable *tab, const uint8_t *ids, const uint32_t *values, int32_t *status,
+                             uint32_t n);
+int rt_linktable_remove_host(rt_linktable *tab, const uint8_t *ids, int32_t *status, uint32_t n);
+int rt_linktable_lookup_host(rt_linktable *tab, const uint8_t *ids, uint32_t *values_out, uint8_t *found_out,
+                             uint32_t n);
+/* rt_token_spans plus the dispatch, one pass over rt_packet_unpack's records.
+ * Per packet: route[i] (below), link[i] = the table's value for the packet's
+ * destination hash or -1, and the span and key for rt_decrypt: tok_off[i] /
+ * tok_len[i] = the packet's data and key_idx[i] = the value where route is
+ * RT_ROUTE_LINK_DECRYPT; an empty span at pkt_off[i] and key_idx 0 elsewhere
+ * (RT_ST_TOO_SHORT in the decrypt, as every dropped packet).  n_keys is the
+ * size of the key set the batch is decrypted with: a found link whose value is
+ * not below it is never decrypted (RT_ROUTE_LINK_PLAIN).
+ * The initiator-only and responder-only rules (LRRTT, the 0xFF keepalive),
+ * whether a channel exists, and the attached-interface check
+ * (Transport.py:2166) stay with the caller, who filters by link[i]. */
+#define RT_ROUTE_NOT_LINK     0  /* unpack failed, destination type not LINK, or neither DATA nor PROOF */
+#define RT_ROUTE_NO_LINK      1  /* a link packet whose id is not in the table: dropped */
+#define RT_ROUTE_LINK_PLAIN   2  /* link found, Link.receive does not decrypt: every PROOF; DATA with context
+                                    KEEPALIVE, RESOURCE, CACHE_REQUEST or one Link.receive has no branch for */
+#define RT_ROUTE_LINK_DECRYPT 3  /* DATA with context NONE, LINKIDENTIFY, REQUEST, RESPONSE, LRRTT, LINKCLOSE,
+                                    RESOURCE_ADV, RESOURCE_REQ, RESOURCE_HMU, RESOURCE_ICL, RESOURCE_RCL, CHANNEL */
+int rt_link_spans(rt_linktable *tab, const rt_packet_fields *fields, const uint64_t *pkt_off, uint32_t n,
+                  uint32_t n_keys, uint64_t *tok_off, uint32_t *tok_len, uint32_t *key_idx, int32_t *link,
+                  uint8_t *route, void *stream);
 
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from

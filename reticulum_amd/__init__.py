@@ -27,6 +27,11 @@ Resource hashmaps: ``resource_hashmap`` / ``build_hashmap`` /
 ``resource_hashes`` / ``verify_resource`` / ``validate_proof`` /
 ``prepare_resource`` (Resource.py:436-439, 698-699, 759-760, 787-790).  Wire-side neighbours
 (HDLC framing, IFAC masking, packet header unpack/pack): ``reticulum_amd.wire``.
+Links (``reticulum_amd.link``): ``LinkTable`` (link id -> key index on the
+device; ``pipeline.inbound(..., links=table)`` finds each packet's link and
+key, Transport.py:2161-2176, Link.py:941-1148), ``derive_link_keys`` (the
+handshake keys of a batch of links, Link.py:348-361) and
+``link_id_from_lr_packet`` (Link.py:336-342).
 
 ``available()`` tells whether the library and a gfx950 device are usable;
 ``reticulum_amd.dropin`` is the import for the reference's one-line swap,
@@ -42,6 +47,8 @@ from .x25519 import exchange, exchange_batch, public_key, public_keys_batch  # n
 from .resource import build_hashmap, get_map_hash, resource_hashmap  # noqa: F401
 from .resource import prepare_resource, resource_hashes, validate_proof, verify_resource  # noqa: F401
 from . import wire  # noqa: F401
+from . import link  # noqa: F401
+from .link import LinkTable, derive_link_keys, link_id_from_lr_packet  # noqa: F401
 from .token import AES, AES_128_CBC, AES_256_CBC, KeySet, Packed, Token, TOKEN_OVERHEAD, token_len  # noqa: F401
 
 __version__ = "0.1.0"

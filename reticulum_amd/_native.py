@@ -17,6 +17,8 @@ RT_F_SORT_BY_LENGTH = 1
 RT_ST_OK, RT_ST_TOO_SHORT, RT_ST_BAD_HMAC, RT_ST_BAD_CT_LEN, RT_ST_BAD_PAD = 0, 1, 2, 3, 4
 RT_KERNEL_GENERAL, RT_KERNEL_ENC_LONG4, RT_KERNEL_ENC_LONG, RT_KERNEL_DEC_LONG2 = 0, 1, 2, 3
 RT_KERNEL_ENC_SPLIT = 4
+RT_LINK_OK, RT_LINK_DUPLICATE, RT_LINK_FULL, RT_LINK_MISSING = 0, 1, 2, 3
+RT_ROUTE_NOT_LINK, RT_ROUTE_NO_LINK, RT_ROUTE_LINK_PLAIN, RT_ROUTE_LINK_DECRYPT = 0, 1, 2, 3
 # the RNSTOK_ABI_VERSION (include/rnstok.h) these bindings are written for;
 # load() refuses any other build of the library
 ABI_VERSION = 3
@@ -81,6 +83,17 @@ SIGNATURES = [
     ("rt_frames_compact_workspace_bytes", _u64, [_u64]),
     ("rt_frames_compact", _int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rt_token_spans", _int, [_vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("rt_linktable_create", _vp, [_vp, _u32]),
+    ("rt_linktable_destroy", None, [_vp]),
+    ("rt_linktable_capacity", _u32, [_vp]),
+    ("rt_linktable_insert", _int, [_vp, _vp, _vp, _vp, _u32, _vp]),
+    ("rt_linktable_remove", _int, [_vp, _vp, _vp, _u32, _vp]),
+    ("rt_linktable_lookup", _int, [_vp, _vp, _vp, _vp, _u32, _vp]),
+    ("rt_linktable_count", _int, [_vp, _vp, _vp]),
+    ("rt_linktable_insert_host", _int, [_vp, _vp, _vp, _vp, _u32]),
+    ("rt_linktable_remove_host", _int, [_vp, _vp, _vp, _u32]),
+    ("rt_linktable_lookup_host", _int, [_vp, _vp, _vp, _vp, _u32]),
+    ("rt_link_spans", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rt_packet_pack_headers", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("rt_device_alloc", _vp, [_vp, _u64]),
     ("rt_device_free", None, [_vp, _vp]),

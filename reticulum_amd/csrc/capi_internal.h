@@ -97,6 +97,16 @@ struct rt_ctx {
     QueueRing queues;
     // rt_clock_stamps: the launch-clock words the token kernels add to, or null
     std::atomic<unsigned long long *> clk{nullptr};
+    // Link tables (capi_link.hip): LINK_REPORTS mapped host words into which a
+    // table's rebuild writes ticket << 32 | live entries.  They live as long as
+    // the context, so a rebuild still in flight when its table is destroyed
+    // writes into memory that exists; a table believes a word only when it
+    // carries the ticket of that table's latest rebuild.
+    static constexpr uint32_t LINK_REPORTS = 1024;
+    std::mutex link_mu;
+    uint64_t *h_link_report = nullptr, *d_link_report = nullptr;
+    uint32_t link_next = 0;
+    std::atomic<uint32_t> link_ticket{0};
 };
 
 struct rt_keyset {

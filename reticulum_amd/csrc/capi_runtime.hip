@@ -349,6 +349,7 @@ void rt_destroy(rt_ctx *c) {
     hipDeviceSynchronize();            // launches on callers' streams may still use the ring
     hipFree(c->d_sbox);
     hipFree(c->queues.d);
+    if (c->h_link_report) hipHostFree(c->h_link_report);
     for (auto &e : c->queues.ev)
         if (e) hipEventDestroy(e);
     if (c->pool) hipMemPoolDestroy(c->pool);

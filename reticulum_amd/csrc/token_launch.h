@@ -246,6 +246,38 @@ hipError_t launch_unpack(const uint8_t *pkt, const uint64_t *off, const uint32_t
                          hipStream_t s);
 hipError_t launch_pack_headers(const PackArgs &a, hipStream_t s);
 
+// Link table and dispatch (link_kernels.hip; the layout is described there).
+struct LinkTab {
+    uint64_t *slots;               // cap slot words
+    uint8_t *ids;                  // cap x 16 B, entry s belongs to slot s
+    uint32_t *values;              // cap
+    uint32_t *live;                // one word: entries present
+    uint32_t cap;                  // a power of two
+};
+struct LinkSpanArgs {
+    const uint8_t *fields;         // n rt_packet_fields records
+    const uint64_t *pkt_off;
+    LinkTab t;
+    uint32_t n_keys;               // values not below it are never a key index
+    uint64_t *tok_off;
+    uint32_t *tok_len, *key_idx;
+    int32_t *link;
+    uint8_t *route;
+    uint32_t n;
+};
+hipError_t launch_link_lookup(const LinkTab &t, const uint8_t *ids, uint32_t *values_out, uint8_t *found_out,
+                              uint32_t n, hipStream_t s);
+// status doubles as the scratch between each call's two kernels
+hipError_t launch_link_insert(const LinkTab &t, const uint8_t *ids, const uint32_t *values, int32_t *status,
+                              uint32_t n, hipStream_t s);
+hipError_t launch_link_remove(const LinkTab &t, const uint8_t *ids, int32_t *status, uint32_t n, hipStream_t s);
+// Rebuild in place through `workspace` (device, link_rebuild_workspace_bytes);
+// `report` (device address of mapped host memory, or null) receives
+// ticket << 32 | live entries.
+uint64_t link_rebuild_workspace_bytes(uint32_t cap);
+hipError_t launch_link_rebuild(const LinkTab &t, void *workspace, uint64_t *report, uint32_t ticket, hipStream_t s);
+hipError_t launch_link_spans(const LinkSpanArgs &a, hipStream_t s);
+
 hipError_t configure_kernels();
 
 // bytes from device memory `src` to pinned host memory, as GPU stores into the

@@ -654,6 +654,85 @@ def token_spans(fields, pkt_off, tok_off, tok_len, stream=None):
                                      _stream(stream, fields.device)))
 
 
+# Link table (link_kernels.hip): ``tab`` is an rt_linktable handle, as
+# reticulum_amd.link.LinkTable holds it; ids are (n, 16) uint8 rows.
+
+LINK_OK, LINK_DUPLICATE, LINK_FULL, LINK_MISSING = 0, 1, 2, 3       # RT_LINK_* (include/rnstok.h)
+ROUTE_NOT_LINK, ROUTE_NO_LINK, ROUTE_LINK_PLAIN, ROUTE_LINK_DECRYPT = 0, 1, 2, 3    # RT_ROUTE_*
+
+
+def _link_ids(ids):
+    _check_u8(ids)
+    if ids.dim() != 2 or ids.shape[1] != 16 or not ids.is_contiguous():
+        raise ValueError("link ids must be a contiguous (n, 16) uint8 tensor")
+    return ids.shape[0]
+
+
+def linktable_insert(tab, ids, values, status, stream=None):
+    """Enter ids[i] -> values[i] ((n,) int32, read as uint32); status (n,)
+    int32 receives LINK_OK, LINK_DUPLICATE (present already, or at a lower
+    index of this batch: the earlier one stays) or LINK_FULL."""
+    n = _link_ids(ids)
+    _check_i32(n, values=values, status=status)
+    if values is None or status is None:
+        raise ValueError("values and status are required")
+    _native.check(_native.load().rt_linktable_insert(tab, _p(ids), _p(values), _p(status), n,
+                                                     _stream(stream, ids.device)))
+
+
+def linktable_remove(tab, ids, status, stream=None):
+    """Remove ids[i]; status (n,) int32 receives LINK_OK or LINK_MISSING."""
+    n = _link_ids(ids)
+    _check_i32(n, status=status)
+    if status is None:
+        raise ValueError("status is required")
+    _native.check(_native.load().rt_linktable_remove(tab, _p(ids), _p(status), n, _stream(stream, ids.device)))
+
+
+def linktable_lookup(tab, ids, values_out, found_out, stream=None):
+    """values_out[i] ((n,) int32) = the value of ids[i], -1 on a miss;
+    found_out[i] ((n,) uint8) = 1 / 0."""
+    n = _link_ids(ids)
+    _check_i32(n, values_out=values_out)
+    _check_u8(found_out)
+    if values_out is None or found_out is None or found_out.numel() != n or not found_out.is_contiguous():
+        raise ValueError(f"values_out must be ({n},) int32 and found_out a contiguous ({n},) uint8 tensor")
+    _native.check(_native.load().rt_linktable_lookup(tab, _p(ids), _p(values_out), _p(found_out), n,
+                                                     _stream(stream, ids.device)))
+
+
+def linktable_count(tab, count_out, stream=None):
+    """count_out (a one-element int32 device tensor) = entries present."""
+    _check_i32(1, count_out=count_out)
+    if count_out is None:
+        raise ValueError("count_out is required")
+    _native.check(_native.load().rt_linktable_count(tab, _p(count_out), _stream(stream, count_out.device)))
+
+
+def link_spans(tab, fields, pkt_off, n_keys, tok_off, tok_len, key_idx, link, route, stream=None):
+    """token_spans plus the link dispatch (Transport.py:2161-2176,
+    Link.py:941-1148) over packet_unpack's records: route[i] ((n,) uint8) is
+    ROUTE_NOT_LINK, ROUTE_NO_LINK, ROUTE_LINK_PLAIN or ROUTE_LINK_DECRYPT,
+    link[i] ((n,) int32) the table's value for the packet's destination hash
+    or -1; where the route is ROUTE_LINK_DECRYPT tok_off[i] / tok_len[i] are
+    the packet's data and key_idx[i] ((n,) int32) the value, elsewhere the
+    span is empty at pkt_off[i] and key_idx 0.  ``n_keys`` is the size of the
+    key set the batch is decrypted with: a link whose value is not below it is
+    never decrypted."""
+    n = pkt_off.numel()
+    if fields.numel() != 96 * n or route.numel() != n:
+        raise ValueError("shape mismatch")
+    _check_u8(fields, route)
+    _check_i64(n, pkt_off=pkt_off, tok_off=tok_off)
+    _check_i32(n, tok_len=tok_len, key_idx=key_idx, link=link)
+    if any(t is None for t in (tok_off, tok_len, key_idx, link)):
+        raise ValueError("tok_off, tok_len, key_idx and link are required")
+    if not 0 <= int(n_keys) <= 0xFFFFFFFF:
+        raise ValueError("n_keys must be a uint32")
+    _native.check(_native.load().rt_link_spans(tab, _p(fields), _p(pkt_off), n, int(n_keys), _p(tok_off), _p(tok_len),
+                                               _p(key_idx), _p(link), _p(route), _stream(stream, fields.device)))
+
+
 def ifac_mask(pkt, pkt_off, pkt_len, ifac, ifac_key, out, out_off, stream=None):
     """Transport.transmit's IFAC step (Transport.py:1069-1101): packet i plus
     its access code ifac[i] (n, ifac_size) -> pkt_len[i] + ifac_size masked

@@ -67,8 +67,10 @@ def ifac_identity(ifac_key):
 
 
 def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=None, flags=None, hops=None,
-             stream=None, aligned=True, ifac_size=None):
-    """n DATA packets of one length L, one link key: pt (n, L) uint8, iv (n,
+             stream=None, aligned=True, ifac_size=None, key_idx=None):
+    """n DATA packets of one length L, one link key (or, with ``key_idx`` (n,)
+    int32, packet i under key key_idx[i] of ``ks``: one call that sends on
+    many links): pt (n, L) uint8, iv (n,
     16), destination_hash (n, 16), context (n,) uint8, flags/hops (n,) uint8
     (default 0: HEADER_1 DATA, hop 0), ifac (n, ifac_size) the access codes
     (the tail of the interface identity's signature of each packet, made by
@@ -99,7 +101,7 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
             stride = pl
             flat = torch.empty(n * stride, dtype=torch.uint8, device=dev)
             raw = flat.view(n, pl)
-        device.encrypt_uniform(ks, pt, L, iv, raw[:, HEADER_1_LEN:], stream=stream)
+        device.encrypt_uniform(ks, pt, L, iv, raw[:, HEADER_1_LEN:], key_idx=key_idx, stream=stream)
         off = torch.arange(n, dtype=torch.int64, device=dev) * stride
         device.pack_headers(flags, hops, destination_hash, context, flat, off, stream=stream)
         if isz:
@@ -123,7 +125,7 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
 
 
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
-            check_ifac=False):
+            check_ifac=False, links=None):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -162,7 +164,18 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     the unmask, Transport.py:1470-1474): a packet whose code is not the tail
     of the interface identity's signature of it gets ``ifac_status`` 2 and is
     dropped there, as the reference returns: unpack reports ok = 0, its token
-    status is TOO_SHORT and nothing of it is decrypted."""
+    status is TOO_SHORT and nothing of it is decrypted.
+
+    ``links`` (a :class:`reticulum_amd.link.LinkTable`) dispatches every packet
+    to its link between unpack and decrypt (device.link_spans in place of
+    token_spans; Transport.py:2161-2176, Link.py:941-1148): a packet is
+    decrypted only when it is a LINK DATA packet whose destination hash is in
+    the table and whose context Link.receive decrypts, and then under key
+    ``key_idx`` = the table's value of ``ks``; every other packet has status
+    TOO_SHORT.  The result gains ``route`` (uint8, device.ROUTE_*), ``link``
+    (the table's value or -1) and ``key_idx`` (int32).  The caller filters by
+    ``link`` for what stays with it: the initiator-only and responder-only
+    contexts, whether a channel exists, and the attached interface."""
     if aligned is None:
         aligned = device.LINE * (max_pairs + 1) <= buf.numel()
     if check_ifac and ifac_size:
@@ -215,16 +228,27 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
         device.packet_unpack(un, f_off, p_len, fields, stream=stream)
         tok_off = torch.empty(max_pairs, dtype=torch.int64, device=dev)
         tok_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
-        device.token_spans(fields, f_off, tok_off, tok_len, stream=stream)
+        key_idx = None
+        if links is not None:
+            key_idx = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            link = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            route = torch.empty(max_pairs, dtype=torch.uint8, device=dev)
+            device.link_spans(links.handle, fields, f_off, ks.n_keys, tok_off, tok_len, key_idx, link, route,
+                              stream=stream)
+        else:
+            device.token_spans(fields, f_off, tok_off, tok_len, stream=stream)
         pt = torch.empty_like(un)
         pt_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
         status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
         # each plaintext (at most its token's length - 48 bytes) is written inside its own token's span
         pt_off = tok_off + pt_shift if pt_shift else tok_off
-        device.decrypt(ks, un, tok_off, tok_len, pt, pt_off, pt_len, status, stream=stream)
-    return {"pt": pt, "pt_off": pt_off, "pt_len": pt_len, "status": status, "ifac": ifac,
-            "ifac_status": ifac_status, "fields": fields, "frame_pair": frame_pair, "n_frames": n_frames,
-            "frame_status": d_st, "frame_len": d_len, "counts": counts}
+        device.decrypt(ks, un, tok_off, tok_len, pt, pt_off, pt_len, status, key_idx=key_idx, stream=stream)
+    res = {"pt": pt, "pt_off": pt_off, "pt_len": pt_len, "status": status, "ifac": ifac,
+           "ifac_status": ifac_status, "fields": fields, "frame_pair": frame_pair, "n_frames": n_frames,
+           "frame_status": d_st, "frame_len": d_len, "counts": counts}
+    if links is not None:
+        res.update(route=route, link=link, key_idx=key_idx)
+    return res
 
 
 def _on(stream):
