@@ -616,6 +616,86 @@ int rt_link_spans(rt_linktable *tab, const rt_packet_fields *fields, const uint6
                   uint32_t n_keys, uint64_t *tok_off, uint32_t *tok_len, uint32_t *key_idx, int32_t *link,
                   uint8_t *route, void *stream);
 
+/* ---- packet hash list and packet filter (Transport.py:1377-1427, 1525-1545, 656-658) */
+/* Transport.inbound drops the packets it has seen before.  A hash list is
+ * Transport.packet_hashlist and packet_hashlist_prev in device memory: two
+ * generations, current and previous, of a set of 32-byte packet hashes, each an
+ * open-addressing table of the link table's build with the smallest power of
+ * two of slots that is at least 2 * max_hashes (rt_hashlist_capacity), holding
+ * at most max_hashes entries; max_hashes is 1 .. 2^29 (the reference's
+ * hashlist_maxsize is 1 000 000).  No hash value is special.
+ *
+ * The calls take DEVICE pointers and a stream and only enqueue; hashes are
+ * n x 32 bytes at any alignment; n == 0 is RT_OK, n is at most 2^30 - 2.  The
+ * _host forms take HOST pointers and return when the outputs are filled.
+ * Calls on one list take effect in the order the host makes them, whatever
+ * their streams, and rt_hashlist_destroy never blocks (the link table's rules).
+ *
+ * rt_packet_filter is packet_filter plus the remember step of
+ * Transport.inbound for the n records rt_packet_unpack wrote, as if the
+ * packets were processed one after another in index order, with
+ * hops = fields[i].hops + 1 (Transport.py:1496).  status[i]:
+ *   RT_FILTER_PASS             handed on;
+ *   RT_FILTER_NO_PACKET        fields[i].ok was 0;
+ *   RT_FILTER_OTHER_TRANSPORT  HEADER_2, not an ANNOUNCE, and the transport id
+ *                              is not transport_identity (16 bytes);
+ *   RT_FILTER_BAD_ANNOUNCE     a PLAIN or GROUP announce, or an announce for
+ *                              another destination type than SINGLE whose hash
+ *                              is in the list;
+ *   RT_FILTER_HOPS             a PLAIN or GROUP packet with hops > 1;
+ *   RT_FILTER_DUPLICATE        the hash is in either generation, or belongs to
+ *                              a packet at a lower index of this batch that
+ *                              passed and was remembered.
+ * Contexts KEEPALIVE, RESOURCE_REQ, RESOURCE_PRF, RESOURCE, CACHE_REQUEST and
+ * CHANNEL, and the PLAIN and GROUP packets that pass, do not consult the list;
+ * a SINGLE announce passes even when its hash is present.  Every packet that
+ * passes is entered into the current generation, except a PROOF with context
+ * LRPROOF and a packet whose destination hash is found in `transit` (an
+ * rt_linktable of the list's context standing for Transport.link_table, the
+ * links this node carries for others; NULL: none).  A hash present in the
+ * previous generation alone makes a duplicate and is not moved; a SINGLE
+ * announce found there passes and is entered into the current one.
+ * A dropped packet also gets fields[i].ok = 0, so that rt_link_spans and
+ * rt_token_spans give it an empty span; the rest of its record stays.
+ * A packet that would be entered when the current generation already holds
+ * max_hashes entries (or finds no free slot) still passes, is not entered, and
+ * adds one to the overflow count.  When the new hashes of one batch outnumber
+ * the room left, as many as there is room for are entered and which of them is
+ * not specified; the caller avoids all this with rt_hashlist_cull.
+ *
+ * rt_hashlist_cull is the job loop's step: when the current generation holds
+ * more than max_hashes / 2 entries it becomes the previous one and the current
+ * one becomes empty; otherwise nothing changes.  Decided on the device: the
+ * call reads nothing back.
+ * rt_hashlist_add enters hashes into the current generation (add_packet_hash:
+ * reloading a saved list, hashes the caller deferred), under the same rule for
+ * a full generation.  rt_hashlist_remove removes from the current generation
+ * only (Transport.py:2186-2187) and writes RT_LINK_OK, or RT_LINK_MISSING where
+ * the hash is not there or is removed at a lower index of this batch.
+ * rt_hashlist_contains writes 0, 1 (current generation) or 2 (previous only).
+ * rt_hashlist_counts writes three words: entries in the current generation,
+ * in the previous one, and the overflow count. */
+#define RT_FILTER_PASS            0
+#define RT_FILTER_NO_PACKET       1
+#define RT_FILTER_OTHER_TRANSPORT 2
+#define RT_FILTER_BAD_ANNOUNCE    3
+#define RT_FILTER_HOPS            4
+#define RT_FILTER_DUPLICATE       5
+typedef struct rt_hashlist rt_hashlist;
+rt_hashlist *rt_hashlist_create(rt_ctx *ctx, uint32_t max_hashes);
+void         rt_hashlist_destroy(rt_hashlist *list);
+uint32_t     rt_hashlist_capacity(const rt_hashlist *list);
+int rt_packet_filter(rt_hashlist *list, rt_linktable *transit, const uint8_t *transport_identity,
+                     rt_packet_fields *fields, uint32_t n, int32_t *status, void *stream);
+int rt_hashlist_cull(rt_hashlist *list, void *stream);
+int rt_hashlist_add(rt_hashlist *list, const uint8_t *hashes, uint32_t n, void *stream);
+int rt_hashlist_remove(rt_hashlist *list, const uint8_t *hashes, uint32_t n, int32_t *status, void *stream);
+int rt_hashlist_contains(rt_hashlist *list, const uint8_t *hashes, uint32_t n, uint8_t *found_out, void *stream);
+int rt_hashlist_counts(rt_hashlist *list, uint32_t *out, void *stream);
+int rt_hashlist_add_host(rt_hashlist *list, const uint8_t *hashes, uint32_t n);
+int rt_hashlist_remove_host(rt_hashlist *list, const uint8_t *hashes, uint32_t n, int32_t *status);
+int rt_hashlist_contains_host(rt_hashlist *list, const uint8_t *hashes, uint32_t n, uint8_t *found_out);
+
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from
  * rt_host_alloc, is written by GPU stores into the mapped buffer on `stream`

@@ -32,6 +32,10 @@ device; ``pipeline.inbound(..., links=table)`` finds each packet's link and
 key, Transport.py:2161-2176, Link.py:941-1148), ``derive_link_keys`` (the
 handshake keys of a batch of links, Link.py:348-361) and
 ``link_id_from_lr_packet`` (Link.py:336-342).
+Replay protection (``reticulum_amd.filter``): ``PacketHashlist``, Transport's
+packet hash list on the device; ``pipeline.inbound(..., seen=list)`` runs
+Transport.packet_filter between unpack and dispatch (Transport.py:1377-1427,
+1525-1545) and ``cull()`` is the job loop's step (Transport.py:656-658).
 
 ``available()`` tells whether the library and a gfx950 device are usable;
 ``reticulum_amd.dropin`` is the import for the reference's one-line swap,
@@ -49,6 +53,8 @@ from .resource import prepare_resource, resource_hashes, validate_proof, verify_
 from . import wire  # noqa: F401
 from . import link  # noqa: F401
 from .link import LinkTable, derive_link_keys, link_id_from_lr_packet  # noqa: F401
+from . import filter  # noqa: F401
+from .filter import PacketHashlist  # noqa: F401
 from .token import AES, AES_128_CBC, AES_256_CBC, KeySet, Packed, Token, TOKEN_OVERHEAD, token_len  # noqa: F401
 
 __version__ = "0.1.0"

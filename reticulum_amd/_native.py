@@ -19,6 +19,8 @@ RT_KERNEL_GENERAL, RT_KERNEL_ENC_LONG4, RT_KERNEL_ENC_LONG, RT_KERNEL_DEC_LONG2 
 RT_KERNEL_ENC_SPLIT = 4
 RT_LINK_OK, RT_LINK_DUPLICATE, RT_LINK_FULL, RT_LINK_MISSING = 0, 1, 2, 3
 RT_ROUTE_NOT_LINK, RT_ROUTE_NO_LINK, RT_ROUTE_LINK_PLAIN, RT_ROUTE_LINK_DECRYPT = 0, 1, 2, 3
+RT_FILTER_PASS, RT_FILTER_NO_PACKET, RT_FILTER_OTHER_TRANSPORT = 0, 1, 2
+RT_FILTER_BAD_ANNOUNCE, RT_FILTER_HOPS, RT_FILTER_DUPLICATE = 3, 4, 5
 # the RNSTOK_ABI_VERSION (include/rnstok.h) these bindings are written for;
 # load() refuses any other build of the library
 ABI_VERSION = 3
@@ -94,6 +96,18 @@ SIGNATURES = [
     ("rt_linktable_remove_host", _int, [_vp, _vp, _vp, _u32]),
     ("rt_linktable_lookup_host", _int, [_vp, _vp, _vp, _vp, _u32]),
     ("rt_link_spans", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("rt_hashlist_create", _vp, [_vp, _u32]),
+    ("rt_hashlist_destroy", None, [_vp]),
+    ("rt_hashlist_capacity", _u32, [_vp]),
+    ("rt_packet_filter", _int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    ("rt_hashlist_cull", _int, [_vp, _vp]),
+    ("rt_hashlist_add", _int, [_vp, _vp, _u32, _vp]),
+    ("rt_hashlist_remove", _int, [_vp, _vp, _u32, _vp, _vp]),
+    ("rt_hashlist_contains", _int, [_vp, _vp, _u32, _vp, _vp]),
+    ("rt_hashlist_counts", _int, [_vp, _vp, _vp]),
+    ("rt_hashlist_add_host", _int, [_vp, _vp, _u32]),
+    ("rt_hashlist_remove_host", _int, [_vp, _vp, _u32, _vp]),
+    ("rt_hashlist_contains_host", _int, [_vp, _vp, _u32, _vp]),
     ("rt_packet_pack_headers", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("rt_device_alloc", _vp, [_vp, _u64]),
     ("rt_device_free", None, [_vp, _vp]),

@@ -3,21 +3,7 @@
 // it.  Device pointers on the caller's stream; the *_host calls go through a
 // staging lane (capi_internal.h).  The kernels are in link_kernels.hip, the
 // host-side arithmetic in link_host.h.
-#include "capi_internal.h"
-#include "link_host.h"
-
-struct rt_linktable {
-    rt_ctx *ctx = nullptr;
-    LinkTab t{};
-    // Calls take effect in host order: `done` is recorded after each call's
-    // launches on its stream `last`, and a call on another stream waits for it.
-    std::mutex mu;
-    hipStream_t last = nullptr;
-    hipEvent_t done = nullptr;
-    LinkBook book;
-    uint32_t report = 0;           // this table's word of ctx->h_link_report
-    uint32_t ticket = 0;           // of the latest rebuild enqueued
-};
+#include "capi_table.h"
 
 namespace {
 
@@ -29,27 +15,6 @@ int check_batch(uint32_t n, const char *who) {
     if (n > LINK_MAX_BATCH) return fail(RT_E_INVAL, std::string(who) + ": at most 2^30 - 2 items per call");
     return RT_OK;
 }
-
-// The frame of one call on a table: holds the table's lock, orders the stream
-// after the call before, and records the call on the way out.
-class TableCall {
-public:
-    TableCall(rt_linktable *tab, hipStream_t s) : tab_(tab), s_(s), g_(tab->mu) {}
-    hipError_t begin() {
-        hipError_t e = hipSetDevice(tab_->ctx->device);
-        if (e == hipSuccess && s_ != tab_->last) e = hipStreamWaitEvent(s_, tab_->done, 0);
-        return e;
-    }
-    hipError_t end() {
-        tab_->last = s_;
-        return hipEventRecord(tab_->done, s_);
-    }
-
-private:
-    rt_linktable *tab_;
-    hipStream_t s_;
-    std::lock_guard<std::mutex> g_;
-};
 
 // The mapped words the rebuilds report into, made with the context's first table.
 bool ensure_reports(rt_ctx *c) {
@@ -89,7 +54,7 @@ hipError_t reclaim(rt_linktable *tab, uint32_t n, hipStream_t s) {
 
 int insert_on(rt_linktable *tab, const uint8_t *ids, const uint32_t *values, int32_t *status, uint32_t n,
               hipStream_t s) {
-    TableCall call(tab, s);
+    TableCall<rt_linktable> call(tab, s);
     RT_HIP(call.begin(), "link table ordering");
     RT_HIP(reclaim(tab, n, s), "link table rebuild");
     RT_HIP(launch_link_insert(tab->t, ids, values, status, n, s), "link insert");
@@ -98,7 +63,7 @@ int insert_on(rt_linktable *tab, const uint8_t *ids, const uint32_t *values, int
     return RT_OK;
 }
 int remove_on(rt_linktable *tab, const uint8_t *ids, int32_t *status, uint32_t n, hipStream_t s) {
-    TableCall call(tab, s);
+    TableCall<rt_linktable> call(tab, s);
     RT_HIP(call.begin(), "link table ordering");
     RT_HIP(launch_link_remove(tab->t, ids, status, n, s), "link remove");
     tab->book.on_remove(n);
@@ -107,7 +72,7 @@ int remove_on(rt_linktable *tab, const uint8_t *ids, int32_t *status, uint32_t n
 }
 int lookup_on(rt_linktable *tab, const uint8_t *ids, uint32_t *values_out, uint8_t *found_out, uint32_t n,
               hipStream_t s) {
-    TableCall call(tab, s);
+    TableCall<rt_linktable> call(tab, s);
     RT_HIP(call.begin(), "link table ordering");
     RT_HIP(launch_link_lookup(tab->t, ids, values_out, found_out, n, s), "link lookup");
     RT_HIP(call.end(), "link table ordering");
@@ -214,7 +179,7 @@ int rt_linktable_count(rt_linktable *tab, uint32_t *count_out, void *stream) {
     RT_TRY(check_table(tab));
     if (!count_out) return fail(RT_E_INVAL, "rt_linktable_count: null count_out");
     hipStream_t s = as_stream(stream);
-    TableCall call(tab, s);
+    TableCall<rt_linktable> call(tab, s);
     RT_HIP(call.begin(), "link table ordering");
     RT_HIP(hipMemcpyAsync(count_out, tab->t.live, 4, hipMemcpyDeviceToDevice, s), "link count");
     RT_HIP(call.end(), "link table ordering");
@@ -278,7 +243,7 @@ int rt_link_spans(rt_linktable *tab, const rt_packet_fields *fields, const uint6
     if (!fields || !pkt_off || !tok_off || !tok_len || !key_idx || !link || !route)
         return fail(RT_E_INVAL, "rt_link_spans: null buffer");
     hipStream_t s = as_stream(stream);
-    TableCall call(tab, s);
+    TableCall<rt_linktable> call(tab, s);
     RT_HIP(call.begin(), "link table ordering");
     LinkSpanArgs a{(const uint8_t *)fields, pkt_off, tab->t, n_keys, tok_off, tok_len, key_idx, link, route, n};
     RT_HIP(launch_link_spans(a, s), "link spans");

@@ -278,6 +278,41 @@ uint64_t link_rebuild_workspace_bytes(uint32_t cap);
 hipError_t launch_link_rebuild(const LinkTab &t, void *workspace, uint64_t *report, uint32_t ticket, hipStream_t s);
 hipError_t launch_link_spans(const LinkSpanArgs &a, hipStream_t s);
 
+// Packet hash list and packet filter (filter_kernels.hip; the layout is
+// described there).  Two generations of slot words and 32-byte hashes; which
+// of them is the current one is a word in device memory that every kernel reads.
+struct HashListState {
+    uint32_t sel;                  // the current generation, 0 or 1
+    uint32_t count[2];             // entries present, by generation
+    uint32_t overflow;             // packets passed but not remembered: the current generation was full
+    uint32_t rotate;               // the latest cull's decision, for its clearing kernel
+    uint32_t pad[3];
+};
+struct HashList {
+    uint64_t *slots[2];            // cap slot words each
+    uint8_t *hashes[2];            // cap x 32 B each, entry s belongs to slot s
+    HashListState *st;
+    uint32_t cap;                  // a power of two
+    uint32_t max;                  // entries a generation holds at most
+};
+struct FilterArgs {
+    HashList l;
+    LinkTab transit;               // slots null: none
+    const uint8_t *identity;       // 16 B
+    uint8_t *fields;               // n rt_packet_fields records
+    int32_t *status;
+    uint32_t n;
+};
+// status doubles as the scratch between each call's kernels
+hipError_t launch_packet_filter(const FilterArgs &a, hipStream_t s);
+hipError_t launch_hashlist_add(const HashList &l, const uint8_t *hashes, int32_t *scratch, uint32_t n, hipStream_t s);
+hipError_t launch_hashlist_remove(const HashList &l, const uint8_t *hashes, int32_t *status, uint32_t n,
+                                  hipStream_t s);
+hipError_t launch_hashlist_contains(const HashList &l, const uint8_t *hashes, uint8_t *found_out, uint32_t n,
+                                    hipStream_t s);
+hipError_t launch_hashlist_cull(const HashList &l, hipStream_t s);
+hipError_t launch_hashlist_counts(const HashList &l, uint32_t *out, hipStream_t s);
+
 hipError_t configure_kernels();
 
 // bytes from device memory `src` to pinned host memory, as GPU stores into the

@@ -733,6 +733,87 @@ def link_spans(tab, fields, pkt_off, n_keys, tok_off, tok_len, key_idx, link, ro
                                                _p(key_idx), _p(link), _p(route), _stream(stream, fields.device)))
 
 
+# Packet hash list and packet filter (filter_kernels.hip): ``lst`` is an
+# rt_hashlist handle, as reticulum_amd.filter.PacketHashlist holds it; hashes
+# are (n, 32) uint8 rows.
+
+FILTER_PASS, FILTER_NO_PACKET, FILTER_OTHER_TRANSPORT = 0, 1, 2       # RT_FILTER_* (include/rnstok.h)
+FILTER_BAD_ANNOUNCE, FILTER_HOPS, FILTER_DUPLICATE = 3, 4, 5
+HASHLIST_ABSENT, HASHLIST_CURRENT, HASHLIST_PREVIOUS = 0, 1, 2
+
+
+def _packet_hashes(hashes):
+    _check_u8(hashes)
+    if hashes.dim() != 2 or hashes.shape[1] != 32 or not hashes.is_contiguous():
+        raise ValueError("packet hashes must be a contiguous (n, 32) uint8 tensor")
+    return hashes.shape[0]
+
+
+def packet_filter(lst, fields, transport_identity, status, transit=None, stream=None):
+    """Transport.packet_filter and the remember step of Transport.inbound
+    (Transport.py:1377-1427, 1525-1545) over packet_unpack's records, as if the
+    packets came one after another in index order: status[i] ((n,) int32) is
+    FILTER_PASS or the rule that dropped the packet, a dropped packet's
+    fields[i].ok becomes 0, and every packet that passes is entered into the
+    list's current generation unless it is a link request proof or its
+    destination hash is in ``transit`` (an rt_linktable handle, or None).
+    ``transport_identity`` is the node's 16-byte transport id on the device."""
+    _check_u8(fields, transport_identity)
+    if fields.dim() != 2 or fields.shape[1] != 96 or not fields.is_contiguous():
+        raise ValueError("fields must be a contiguous (n, 96) uint8 tensor")
+    n = fields.shape[0]
+    if transport_identity.numel() != 16 or not transport_identity.is_contiguous():
+        raise ValueError("transport_identity must be 16 contiguous bytes")
+    _check_i32(n, status=status)
+    if status is None:
+        raise ValueError("status is required")
+    _native.check(_native.load().rt_packet_filter(lst, transit, _p(transport_identity), _p(fields), n, _p(status),
+                                                  _stream(stream, fields.device)))
+
+
+def hashlist_cull(lst, device, stream=None):
+    """The job loop's step (Transport.py:656-658): the current generation
+    becomes the previous one when it holds more than max_hashes // 2 entries.
+    Decided on the device; nothing is read back."""
+    _native.check(_native.load().rt_hashlist_cull(lst, _stream(stream, device)))
+
+
+def hashlist_add(lst, hashes, stream=None):
+    """Enter hashes[i] into the current generation (Transport.add_packet_hash)."""
+    n = _packet_hashes(hashes)
+    _native.check(_native.load().rt_hashlist_add(lst, _p(hashes), n, _stream(stream, hashes.device)))
+
+
+def hashlist_remove(lst, hashes, status, stream=None):
+    """Remove hashes[i] from the current generation; status (n,) int32
+    receives LINK_OK or LINK_MISSING."""
+    n = _packet_hashes(hashes)
+    _check_i32(n, status=status)
+    if status is None:
+        raise ValueError("status is required")
+    _native.check(_native.load().rt_hashlist_remove(lst, _p(hashes), n, _p(status), _stream(stream, hashes.device)))
+
+
+def hashlist_contains(lst, hashes, found_out, stream=None):
+    """found_out[i] ((n,) uint8) = HASHLIST_ABSENT, HASHLIST_CURRENT or
+    HASHLIST_PREVIOUS (in the previous generation only)."""
+    n = _packet_hashes(hashes)
+    _check_u8(found_out)
+    if found_out is None or found_out.numel() != n or not found_out.is_contiguous():
+        raise ValueError(f"found_out must be a contiguous ({n},) uint8 tensor")
+    _native.check(_native.load().rt_hashlist_contains(lst, _p(hashes), n, _p(found_out),
+                                                      _stream(stream, hashes.device)))
+
+
+def hashlist_counts(lst, out, stream=None):
+    """out (a three-element int32 device tensor) = entries in the current
+    generation, in the previous one, and the overflow count."""
+    _check_i32(3, out=out)
+    if out is None:
+        raise ValueError("out is required")
+    _native.check(_native.load().rt_hashlist_counts(lst, _p(out), _stream(stream, out.device)))
+
+
 def ifac_mask(pkt, pkt_off, pkt_len, ifac, ifac_key, out, out_off, stream=None):
     """Transport.transmit's IFAC step (Transport.py:1069-1101): packet i plus
     its access code ifac[i] (n, ifac_size) -> pkt_len[i] + ifac_size masked

@@ -15,6 +15,7 @@ Inbound, as the interface's read loop hands frames to Transport:
     IFAC check               Transport.py:1470-1474 (with check_ifac; else
                              `ifac` is returned for the caller's own check)
     Packet.unpack + hash     Packet.py:242-275, 342-353
+    packet filter            Transport.py:1377-1427, 1525-1545 (with seen)
     Token.decrypt            Token.py:100-114 (Link/Identity.decrypt)
 
 Every stage is one of reticulum_amd.device's kernels, the rearranging of
@@ -125,7 +126,7 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
 
 
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
-            check_ifac=False, links=None):
+            check_ifac=False, links=None, seen=None, transport_identity=None, transit=None):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -175,7 +176,28 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     TOO_SHORT.  The result gains ``route`` (uint8, device.ROUTE_*), ``link``
     (the table's value or -1) and ``key_idx`` (int32).  The caller filters by
     ``link`` for what stays with it: the initiator-only and responder-only
-    contexts, whether a channel exists, and the attached interface."""
+    contexts, whether a channel exists, and the attached interface.
+
+    ``seen`` (a :class:`reticulum_amd.filter.PacketHashlist`) runs
+    Transport.packet_filter and the remember step of Transport.inbound between
+    unpack and the spans (device.packet_filter; Transport.py:1377-1427,
+    1525-1545), with or without ``links``, over the frames in stream order: a
+    packet for another transport node than ``transport_identity`` (required
+    with ``seen``: the node's 16-byte transport id, uint8 on the device), a
+    PLAIN or GROUP packet from further than one hop and a packet whose hash the
+    list holds are dropped as every other dropped packet is (ok = 0 in
+    ``fields``, an empty span, status TOO_SHORT), and a packet that passes is
+    remembered unless it is a link request proof or its destination hash is in
+    ``transit`` (a LinkTable standing for Transport.link_table, the links this
+    node carries for others).  A packet the access-code check dropped never
+    reaches the list.  The result gains ``filter_status`` (int32 per frame,
+    device.FILTER_*).  Calling ``seen.cull()`` is the caller's part, as the
+    reference's job loop does it.  Out of scope: the hop decrement for
+    local-client and shared-instance interfaces (Transport.py:1520-1523), and
+    a node connected to a shared instance, for which the reference's filter
+    always passes and remembers nothing: such a node passes ``seen=None``."""
+    if seen is not None and transport_identity is None:
+        raise ValueError("seen needs transport_identity, the node's 16-byte transport id")
     if aligned is None:
         aligned = device.LINE * (max_pairs + 1) <= buf.numel()
     if check_ifac and ifac_size:
@@ -226,6 +248,8 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
             p_len = torch.where(drop, torch.zeros_like(f_len), f_len)
         fields = torch.empty((max_pairs, 96), dtype=torch.uint8, device=dev)
         device.packet_unpack(un, f_off, p_len, fields, stream=stream)
+        if seen is not None:
+            filter_status = seen.filter(fields, transport_identity, transit=transit, stream=stream)
         tok_off = torch.empty(max_pairs, dtype=torch.int64, device=dev)
         tok_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
         key_idx = None
@@ -248,6 +272,8 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
            "frame_status": d_st, "frame_len": d_len, "counts": counts}
     if links is not None:
         res.update(route=route, link=link, key_idx=key_idx)
+    if seen is not None:
+        res["filter_status"] = filter_status
     return res
 
 
