@@ -33,6 +33,9 @@
  *   rt_token_spans     packet.data (the token)   RNS/Packet.py:262-275 (data after the header)
  *   rt_linktable_* /   the link of a DATA packet  RNS/Transport.py:2161-2176 (first link in
  *   rt_link_spans      and whether it is decrypted  active_links with the link_id), RNS/Link.py:941-1148
+ *   rt_hashlist_* /    packets seen before        RNS/Transport.py:1377-1427, 1525-1545, 656-658
+ *   rt_packet_filter
+ *   rt_announce_validate  validate_announce       RNS/Identity.py:505-606 (Transport.py:1748-1750, 1772)
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
@@ -695,6 +698,41 @@ int rt_hashlist_counts(rt_hashlist *list, uint32_t *out, void *stream);
 int rt_hashlist_add_host(rt_hashlist *list, const uint8_t *hashes, uint32_t n);
 int rt_hashlist_remove_host(rt_hashlist *list, const uint8_t *hashes, uint32_t n, int32_t *status);
 int rt_hashlist_contains_host(rt_hashlist *list, const uint8_t *hashes, uint32_t n, uint8_t *found_out);
+
+/* ---- announce validation (Identity.py:505-606; Transport.py:1748-1750, 1772) */
+/* Transport.inbound runs Identity.validate_announce(packet,
+ * only_validate_signature=True) on every announce (Transport.py:1748-1750) and
+ * the full validate_announce on those not addressed to a local destination
+ * (:1772).  rt_announce_validate answers both for the n records
+ * rt_packet_unpack wrote (after rt_packet_filter where there is one: a dropped
+ * packet has ok = 0), reading each announce inside its packet at
+ * pkt + pkt_off[i]: data = public key (64) ‖ name hash (10) ‖ random hash (10)
+ * ‖ [ratchet (32), with the context flag] ‖ signature (64) ‖ app data, the
+ * signed data being destination hash ‖ data without the signature
+ * (Identity.py:505-545), verified as rt_ed25519_verify verifies (the
+ * reference's internal provider, every acceptance rule of it).  status[i]:
+ *   only_validate_signature=True returns True  for RT_ANNOUNCE_VALID and
+ *                                              RT_ANNOUNCE_BAD_DESTINATION;
+ *   the full check returns True                for RT_ANNOUNCE_VALID alone,
+ * given that nothing of the caller's part below rejects the announce.
+ * identity_hash (n x 16, may be NULL) receives the announced identity's hash,
+ * SHA-256(public key)[:16], for every record whose signature was checked
+ * (VALID, BAD_SIGNATURE, BAD_DESTINATION) and zeros for the others.  It is the
+ * handle for what stays with the caller: Transport.blackholed_identities
+ * (Identity.py:553-556), the known_destinations public-key collision check
+ * (:569-575), Identity.remember (:577), ratchet bookkeeping (:595) and ingress
+ * limiting (Transport.py:1752-1768).
+ * DEVICE pointers; the call only enqueues on the stream and never
+ * synchronises (its temporary, n + 16 words, comes from the context's
+ * stream-ordered pool).  n == 0 is RT_OK; pkt, pkt_off, fields or status NULL
+ * is RT_E_INVAL. */
+#define RT_ANNOUNCE_VALID            0
+#define RT_ANNOUNCE_NOT_ANNOUNCE     1   /* fields[i].ok == 0 or another packet type: nothing checked */
+#define RT_ANNOUNCE_SHORT            2   /* data shorter than key, name hash, random hash, [ratchet,] signature */
+#define RT_ANNOUNCE_BAD_SIGNATURE    3
+#define RT_ANNOUNCE_BAD_DESTINATION  4   /* signature valid (line 1749 passes), destination hash not of this identity (line 1772 fails) */
+int rt_announce_validate(rt_ctx *ctx, const uint8_t *pkt, const uint64_t *pkt_off, const rt_packet_fields *fields,
+                         uint32_t n, int32_t *status, uint8_t *identity_hash /* n x 16, may be NULL */, void *stream);
 
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from

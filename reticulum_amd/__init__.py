@@ -36,6 +36,9 @@ Replay protection (``reticulum_amd.filter``): ``PacketHashlist``, Transport's
 packet hash list on the device; ``pipeline.inbound(..., seen=list)`` runs
 Transport.packet_filter between unpack and dispatch (Transport.py:1377-1427,
 1525-1545) and ``cull()`` is the job loop's step (Transport.py:656-658).
+Announces: ``pipeline.inbound(..., announces=True)`` validates every announce
+of a read inside its packet (Identity.validate_announce, Identity.py:505-606;
+``device.announce_validate`` is the stage alone).
 
 ``available()`` tells whether the library and a gfx950 device are usable;
 ``reticulum_amd.dropin`` is the import for the reference's one-line swap,

@@ -21,6 +21,8 @@ RT_LINK_OK, RT_LINK_DUPLICATE, RT_LINK_FULL, RT_LINK_MISSING = 0, 1, 2, 3
 RT_ROUTE_NOT_LINK, RT_ROUTE_NO_LINK, RT_ROUTE_LINK_PLAIN, RT_ROUTE_LINK_DECRYPT = 0, 1, 2, 3
 RT_FILTER_PASS, RT_FILTER_NO_PACKET, RT_FILTER_OTHER_TRANSPORT = 0, 1, 2
 RT_FILTER_BAD_ANNOUNCE, RT_FILTER_HOPS, RT_FILTER_DUPLICATE = 3, 4, 5
+RT_ANNOUNCE_VALID, RT_ANNOUNCE_NOT_ANNOUNCE, RT_ANNOUNCE_SHORT = 0, 1, 2
+RT_ANNOUNCE_BAD_SIGNATURE, RT_ANNOUNCE_BAD_DESTINATION = 3, 4
 # the RNSTOK_ABI_VERSION (include/rnstok.h) these bindings are written for;
 # load() refuses any other build of the library
 ABI_VERSION = 3
@@ -108,6 +110,7 @@ SIGNATURES = [
     ("rt_hashlist_add_host", _int, [_vp, _vp, _u32]),
     ("rt_hashlist_remove_host", _int, [_vp, _vp, _u32, _vp]),
     ("rt_hashlist_contains_host", _int, [_vp, _vp, _u32, _vp]),
+    ("rt_announce_validate", _int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("rt_packet_pack_headers", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("rt_device_alloc", _vp, [_vp, _u64]),
     ("rt_device_free", None, [_vp, _vp]),

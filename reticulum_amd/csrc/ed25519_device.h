@@ -126,6 +126,68 @@ X25519_FN void sha512_head_msg(uint64_t st[8], const uint64_t *head, const uint8
     }
 }
 
+// A message that is three spans of one buffer, read in place: message byte m
+// is base[m] below cut1, base[m + gap1] from cut1 to below cut2 and
+// base[m + gap1 + gap2] from cut2 on (cut1 <= cut2 <= len).  An announce's
+// signed data (Identity.py:558-561) is the destination hash, 16 bytes that end
+// one byte before the packet's data (the context byte lies between), then the
+// data without its signature: base = data - 17, cut1 = 16, gap1 = 1,
+// cut2 = 16 + the signature's offset in the data, gap2 = 64,
+// len = 16 + data_len - 64.
+struct sha512_spans {
+    const uint8_t *base;
+    uint32_t cut1, gap1, cut2, gap2, len;
+};
+
+// Where message byte m lies, as an offset from base
+X25519_FN uint64_t sha512_spans_at(const sha512_spans &s, uint64_t m) {
+    return m + (m >= s.cut1 ? s.gap1 : 0u) + (m >= s.cut2 ? s.gap2 : 0u);
+}
+
+// sha512_msg_word for a message in spans.  A word inside one span and below
+// len is read whole; one that straddles a cut or the message's end goes byte
+// by byte, each byte placed on its own.  The highest address read is that of
+// message byte len - 1: nothing of the gaps and nothing at or past
+// base + len + gap1 + gap2.
+X25519_FN uint64_t sha512_spans_word(const sha512_spans &s, uint64_t off) {
+    uint64_t v = 0;
+    const uint64_t at = sha512_spans_at(s, off);
+    if (off + 8 <= (uint64_t)s.len && sha512_spans_at(s, off + 7) == at + 7) {
+        X25519_UNROLL
+        for (int j = 0; j < 8; ++j) v = (v << 8) | s.base[at + j];
+    } else {
+        X25519_UNROLL
+        for (int j = 0; j < 8; ++j) {
+            const uint64_t idx = off + j;
+            uint32_t byte = idx == (uint64_t)s.len ? 0x80u : 0u;
+            if (idx < (uint64_t)s.len) byte = s.base[sha512_spans_at(s, idx)];
+            v = (v << 8) | byte;
+        }
+    }
+    return v;
+}
+
+// sha512_head_msg for a message in spans: st = SHA-512(head ‖ spans)
+template <int HW>
+X25519_FN void sha512_head_spans(uint64_t st[8], const uint64_t *head, const sha512_spans &s) {
+    sha512_init(st);
+    const uint64_t total = 8u * HW + (uint64_t)s.len;
+    const uint32_t nblk = (uint32_t)((total + 17u + 127u) >> 7);
+    X25519_NO_UNROLL
+    for (uint32_t b = 0; b < nblk; ++b) {
+        uint64_t w[16];
+        X25519_UNROLL
+        for (int k = 0; k < 16; ++k) {
+            if (k < HW && b == 0)
+                w[k] = head[k];
+            else
+                w[k] = sha512_spans_word(s, (uint64_t)b * 128u + 8u * k - 8u * HW);
+        }
+        if (b == nblk - 1) w[15] = total << 3;
+        sha512_block(st, w);
+    }
+}
+
 // The 64 digest bytes as 16 little-endian words (Hint: the digest as a
 // little-endian integer)
 X25519_FN void sha512_le_words(uint32_t w[16], const uint64_t st[8]) {
@@ -686,6 +748,55 @@ X25519_FN uint32_t ed25519_verify_words(const uint32_t pk[8], const uint32_t sig
         ge_cached na, bma;
         ge_cached_neg_affine(na, ax, ay);
         ok &= ge_in_subgroup(na);                        // [L](-A) = -[L]A
+        ge b;
+        b.X = fe_bx();
+        b.Y = fe_by();
+        fe_set(b.Z, 1u);
+        fe_mul(b.T, b.X, b.Y);
+        ge_add_cached(b, b, na);
+        ge_to_cached(bma, b);
+        ge_double_scalar(q, s, h, na, bma);
+    }
+    fe rx, ry, t;
+    ok &= ge_decode(rx, ry, sig_r);
+    fe_mul(t, rx, q.Z);
+    ok &= fe_equal(q.X, t);
+    fe_mul(t, ry, q.Z);
+    ok &= fe_equal(q.Y, t);
+    return ok;
+}
+
+// ed_hint and ed25519_verify_words for a message in spans (an announce checked
+// inside its packet): the same stages in the same order and every acceptance
+// rule above, only h comes through the span reader.  Kept as functions of
+// their own so that the code of the kernels that verify one contiguous message
+// stays as it is.
+X25519_FN void ed_hint_spans(uint32_t h[8], const uint32_t first[8], const uint32_t second[8],
+                             const sha512_spans &m) {
+    uint64_t head[8], st[8];
+    sha512_head_from_le(head, first);
+    sha512_head_from_le(head + 4, second);
+    sha512_head_spans<8>(st, head, m);
+    uint32_t d[16];
+    sha512_le_words(d, st);
+    sc_reduce<16>(h, d);
+}
+
+X25519_FN uint32_t ed25519_verify_spans(const uint32_t pk[8], const uint32_t sig_r[8], const uint32_t sig_s[8],
+                                        const sha512_spans &m) {
+    uint32_t ok = (ed_is_zero_bytes(pk) | ed_is_zero_bytes(sig_r)) ^ 1u;
+    uint32_t h[8], s[8];
+    ed_hint_spans(h, sig_r, pk, m);
+    sc_reduce<8>(s, sig_s);
+    ge q;
+    {
+        fe ax, ay, one;
+        ok &= ge_decode(ax, ay, pk);
+        fe_set(one, 1u);
+        ok &= ((fe_is_zero(ax) & fe_equal(ay, one)) & words_nonzero(h)) ^ 1u;
+        ge_cached na, bma;
+        ge_cached_neg_affine(na, ax, ay);
+        ok &= ge_in_subgroup(na);
         ge b;
         b.X = fe_bx();
         b.Y = fe_by();

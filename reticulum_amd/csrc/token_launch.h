@@ -158,6 +158,23 @@ struct IfacSignArgs {
 };
 hipError_t launch_ifac_sign(const IfacSignArgs &a, hipStream_t s);
 
+// Announce validation over rt_packet_unpack's records (announce_kernels.hip):
+// status[i] = RT_ANNOUNCE_*; identity (n x 16, may be null) receives the
+// announced identity's hash, zeros for a record that is no candidate.
+// `work` is announce_workspace_bytes(n) of device memory the launch may use
+// until it has run: the candidate count and the candidates' indices.
+struct AnnounceArgs {
+    const uint8_t *pkt;
+    const uint64_t *pkt_off;
+    const uint8_t *fields;         // n rt_packet_fields records
+    int32_t *status;
+    uint8_t *identity;
+    uint32_t *work;
+    uint32_t n;
+};
+uint64_t announce_workspace_bytes(uint32_t n);
+hipError_t launch_announce_validate(const AnnounceArgs &a, hipStream_t s);
+
 // Resource map hashes (resource_kernels.hip): part j = data + part_off[j]
 // (part_len[j] bytes), or with part_off null the uniform segmentation
 // data[j*sdu, min((j+1)*sdu, size)); salt = salts + part_res[j]*salt_len.

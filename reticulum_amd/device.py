@@ -814,6 +814,50 @@ def hashlist_counts(lst, out, stream=None):
     _native.check(_native.load().rt_hashlist_counts(lst, _p(out), _stream(stream, out.device)))
 
 
+# Announce validation (announce_kernels.hip)
+
+ANNOUNCE_VALID, ANNOUNCE_NOT_ANNOUNCE, ANNOUNCE_SHORT = 0, 1, 2       # RT_ANNOUNCE_* (include/rnstok.h)
+ANNOUNCE_BAD_SIGNATURE, ANNOUNCE_BAD_DESTINATION = 3, 4
+
+
+def announce_validate(pkt, pkt_off, fields, status, identity_hash=None, stream=None):
+    """Identity.validate_announce (Identity.py:505-606) over packet_unpack's
+    records, each announce read inside its packet pkt[pkt_off[i]:]: status[i]
+    ((n,) int32) is ANNOUNCE_VALID, ANNOUNCE_NOT_ANNOUNCE (fields[i].ok is 0, or
+    another packet type), ANNOUNCE_SHORT, ANNOUNCE_BAD_SIGNATURE or
+    ANNOUNCE_BAD_DESTINATION (the signature holds, the destination hash is not
+    this identity's).  validate_announce(only_validate_signature=True)
+    (Transport.py:1748-1750) is true for VALID and BAD_DESTINATION, the full
+    check (:1772) for VALID.  identity_hash ((n, 16) uint8, optional) receives
+    the announced identity's hash where the signature was checked and zeros
+    elsewhere: the handle for the caller's part (blackholed identities, the
+    known-destination key check, Identity.remember, ratchets, ingress limits).
+    Nothing is synchronised."""
+    _check_u8(pkt, fields, identity_hash)
+    if fields.dim() != 2 or fields.shape[1] != 96 or not fields.is_contiguous():
+        raise ValueError("fields must be a contiguous (n, 96) uint8 tensor")
+    n = fields.shape[0]
+    if pkt.dim() != 1:
+        raise ValueError("pkt must be a flat uint8 buffer")
+    _check_i64(n, pkt_off=pkt_off)
+    _check_i32(n, status=status)
+    if pkt_off is None or status is None:
+        raise ValueError("pkt_off and status are required")
+    if identity_hash is not None and (identity_hash.dim() != 2 or identity_hash.shape != (n, 16)
+                                      or not identity_hash.is_contiguous()):
+        raise ValueError(f"identity_hash must be a contiguous ({n}, 16) uint8 tensor")
+    if not pkt.is_cuda or not pkt.is_contiguous():
+        raise ValueError("device API needs contiguous tensors in device memory")
+    for t in (pkt_off, fields, status, identity_hash):
+        if t is not None and t.device != pkt.device:
+            raise ValueError(f"every array must be on the packets' device {pkt.device}, one is on {t.device}")
+    if n == 0:
+        return
+    lib = _native.load()
+    _native.check(lib.rt_announce_validate(_ctx_of(pkt), _p(pkt), _p(pkt_off), _p(fields), n, _p(status),
+                                           _p(identity_hash), _stream(stream, pkt.device)))
+
+
 def ifac_mask(pkt, pkt_off, pkt_len, ifac, ifac_key, out, out_off, stream=None):
     """Transport.transmit's IFAC step (Transport.py:1069-1101): packet i plus
     its access code ifac[i] (n, ifac_size) -> pkt_len[i] + ifac_size masked

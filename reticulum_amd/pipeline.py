@@ -16,6 +16,8 @@ Inbound, as the interface's read loop hands frames to Transport:
                              `ifac` is returned for the caller's own check)
     Packet.unpack + hash     Packet.py:242-275, 342-353
     packet filter            Transport.py:1377-1427, 1525-1545 (with seen)
+    announce validation      Identity.py:505-606, Transport.py:1748-1750, 1772
+                             (with announces)
     Token.decrypt            Token.py:100-114 (Link/Identity.decrypt)
 
 Every stage is one of reticulum_amd.device's kernels, the rearranging of
@@ -126,7 +128,7 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
 
 
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
-            check_ifac=False, links=None, seen=None, transport_identity=None, transit=None):
+            check_ifac=False, links=None, seen=None, transport_identity=None, transit=None, announces=False):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -195,7 +197,22 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     reference's job loop does it.  Out of scope: the hop decrement for
     local-client and shared-instance interfaces (Transport.py:1520-1523), and
     a node connected to a shared instance, for which the reference's filter
-    always passes and remembers nothing: such a node passes ``seen=None``."""
+    always passes and remembers nothing: such a node passes ``seen=None``.
+
+    ``announces`` validates every announce of the read where it lies in its
+    packet (device.announce_validate, after unpack and after the packet filter
+    when ``seen`` is given; Identity.validate_announce, Identity.py:505-606).
+    The result gains ``announce_status`` (int32 per frame, device.ANNOUNCE_*)
+    and ``announce_identity`` (uint8, max_pairs x 16: the announced identity's
+    hash where the signature was checked, zeros elsewhere).
+    validate_announce(only_validate_signature=True) (Transport.py:1748-1750) is
+    true for ANNOUNCE_VALID and ANNOUNCE_BAD_DESTINATION, the full check
+    (:1772) for ANNOUNCE_VALID; an announce that an earlier stage dropped (a
+    forged access code with ``check_ifac``, a replay with ``seen``) has ok = 0
+    and reads ANNOUNCE_NOT_ANNOUNCE like every frame that is no announce.
+    Spans, link dispatch and decrypt are untouched.  Blackholed identities, the
+    known-destination key check, Identity.remember, ratchets and ingress
+    limiting stay with the caller, keyed by ``announce_identity``."""
     if seen is not None and transport_identity is None:
         raise ValueError("seen needs transport_identity, the node's 16-byte transport id")
     if aligned is None:
@@ -250,6 +267,10 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
         device.packet_unpack(un, f_off, p_len, fields, stream=stream)
         if seen is not None:
             filter_status = seen.filter(fields, transport_identity, transit=transit, stream=stream)
+        if announces:
+            announce_status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            announce_identity = torch.empty((max_pairs, 16), dtype=torch.uint8, device=dev)
+            device.announce_validate(un, f_off, fields, announce_status, announce_identity, stream=stream)
         tok_off = torch.empty(max_pairs, dtype=torch.int64, device=dev)
         tok_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
         key_idx = None
@@ -274,6 +295,8 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
         res.update(route=route, link=link, key_idx=key_idx)
     if seen is not None:
         res["filter_status"] = filter_status
+    if announces:
+        res.update(announce_status=announce_status, announce_identity=announce_identity)
     return res
 
 
