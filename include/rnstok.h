@@ -36,6 +36,10 @@
  *   rt_hashlist_* /    packets seen before        RNS/Transport.py:1377-1427, 1525-1545, 656-658
  *   rt_packet_filter
  *   rt_announce_validate  validate_announce       RNS/Identity.py:505-606 (Transport.py:1748-1750, 1772)
+ *   rt_link_prove      Packet.prove on a link     RNS/Link.py:943-955, 1140-1145 (whether), :378-389 and
+ *                                                RNS/Packet.py:199-200 (the proof packet)
+ *   rt_receipt_store / Transport.receipts and     RNS/Transport.py:2326-2363 (the receipt of a link proof),
+ *   rt_proof_settle    validate_link_proof        RNS/Packet.py:434-459
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
@@ -733,6 +737,84 @@ int rt_hashlist_contains_host(rt_hashlist *list, const uint8_t *hashes, uint32_t
 #define RT_ANNOUNCE_BAD_DESTINATION  4   /* signature valid (line 1749 passes), destination hash not of this identity (line 1772 fails) */
 int rt_announce_validate(rt_ctx *ctx, const uint8_t *pkt, const uint64_t *pkt_off, const rt_packet_fields *fields,
                          uint32_t n, int32_t *status, uint8_t *identity_hash /* n x 16, may be NULL */, void *stream);
+
+/* ---- packet proofs on a link (Link.py:378-389, 943-955, 1140-1145; Transport.py:2326-2363) */
+/* Both directions of the packet proof, over the n records rt_packet_unpack
+ * wrote and what rt_link_spans made of them.  The links' signing rows are
+ * indexed by the link table's value l (the index of the link's key): seeds
+ * and publics 32 bytes each at l*key_stride (key_stride 0: one row for every
+ * link, responder links that share their owner's key; else at least 32;
+ * publics is rt_ed25519_public of seeds and trusted), flags one byte each,
+ * peer_publics 32 bytes each at 32*l (the link's peer_sig_pub).  DEVICE
+ * pointers; the calls only enqueue on the stream and never synchronise (their
+ * temporaries, n + 16 and 2n + 16 words, come from the context's
+ * stream-ordered pool).  n == 0 is RT_OK; a NULL required pointer is RT_E_INVAL.
+ *
+ * rt_link_prove is Link.receive's packet.prove().  Record i is proved when
+ * fields[i].ok, it is a DATA packet, link[i] is 0 .. n_links-1 and either
+ *   - its context is NONE, route[i] is RT_ROUTE_LINK_DECRYPT, token_status[i]
+ *     (rt_decrypt's) is RT_ST_OK and flags[link[i]] has RT_LINK_PROVE_ALL, or
+ *   - its context is CHANNEL and flags[link[i]] has RT_LINK_HAS_CHANNEL,
+ *     whatever the token's status: the reference proves before it decrypts.
+ * Then proof_len[i] = 115 and proofs + i*proof_stride (proof_stride >= 115)
+ * receives the packet Link.prove_packet sends: flags 0x0F, hops 0, the link id
+ * (the record's destination hash), context 0x00, the packet hash and its
+ * signature under seeds[link[i]], rt_ed25519_sign's bit for bit with the
+ * fixed-base multiplication from a table, constant time in the seed.  Every
+ * other record gets proof_len[i] = 0 and its row is not written.  Links whose
+ * destination proves by callback (PROVE_APP) get flags 0; the caller signs
+ * what its callback picks with rt_ed25519_sign over the records' packet_hash.
+ *
+ * A receipt table is Transport.receipts on the device: an rt_linktable whose
+ * ids are the first 16 bytes of a packet hash and whose values are receipt ids
+ * 0 .. max_receipts-1 of the caller's choosing, beside receipt_hashes
+ * (max_receipts x 32 bytes, DEVICE, the caller's), the full hash by id.
+ * Adding receipts is rt_linktable_insert (hash[:16], id) followed by
+ * rt_receipt_store over the same batch and the status the insert wrote:
+ * receipt_hashes[ids[i]] = hashes[i] (n x 32) where status[i] is RT_LINK_OK
+ * and ids[i] < max_receipts, so a duplicate leaves the earlier entry and its
+ * hash untouched.  Timeouts and culling are rt_linktable_remove.
+ *
+ * rt_proof_settle is the last branch of Transport.inbound's PROOF handling
+ * with PacketReceipt.validate_link_proof, as if the packets came one after
+ * another in index order.  proof_status[i], the first rule that applies:
+ *   RT_PROOF_NOT_PROOF      fields[i].ok == 0, not a PROOF, or context LRPROOF
+ *                           (0xFF) or RESOURCE_PRF (0x05);
+ *   RT_PROOF_NOT_LINK       a PROOF whose destination type is not LINK: proofs
+ *                           for SINGLE destinations stay with the caller;
+ *   RT_PROOF_NO_LINK        link[i] is not 0 .. n_links-1 (rt_link_spans gives
+ *                           -1 for an id that is not in the link table);
+ *   RT_PROOF_SHORT          data shorter than 96 bytes;
+ *   RT_PROOF_NO_RECEIPT     no receipt holds data[:32], compared in full, or a
+ *                           proof at a lower index of this batch delivered it;
+ *   RT_PROOF_BAD_SIGNATURE  data[32:96] is not peer_publics[link[i]]'s
+ *                           signature of data[:32], as rt_ed25519_verify judges;
+ *   RT_PROOF_DELIVERED      verified: receipt[i] is the receipt's id and the
+ *                           entry is removed from the table inside the call.
+ * receipt[i] is -1 for every other status.  Data past 96 bytes is ignored
+ * (Transport.py:2334-2335 tries every receipt then, Packet.py:436-441 slices).
+ * When one valid proof comes several times in a batch the lowest index is
+ * delivered whatever the scheduling, and a copy with a bad signature below it
+ * does not stand in its way. */
+#define RT_LINK_PROVE_ALL   1u
+#define RT_LINK_HAS_CHANNEL 2u
+#define RT_PROOF_DELIVERED     0
+#define RT_PROOF_NOT_PROOF     1
+#define RT_PROOF_NOT_LINK      2
+#define RT_PROOF_NO_LINK       3
+#define RT_PROOF_SHORT         4
+#define RT_PROOF_NO_RECEIPT    5
+#define RT_PROOF_BAD_SIGNATURE 6
+int rt_link_prove(rt_ctx *ctx, const rt_packet_fields *fields, const uint8_t *route, const int32_t *link,
+                  const int32_t *token_status, const uint8_t *seeds, const uint8_t *publics, uint64_t key_stride,
+                  const uint8_t *flags, uint32_t n_links, uint8_t *proofs, uint64_t proof_stride, uint32_t *proof_len,
+                  uint32_t n, void *stream);
+int rt_receipt_store(rt_linktable *receipts, uint8_t *receipt_hashes, uint32_t max_receipts, const uint8_t *hashes,
+                     const uint32_t *ids, const int32_t *status, uint32_t n, void *stream);
+int rt_proof_settle(rt_linktable *receipts, const uint8_t *receipt_hashes, uint32_t max_receipts, const uint8_t *pkt,
+                    const uint64_t *pkt_off, const rt_packet_fields *fields, const int32_t *link,
+                    const uint8_t *peer_publics, uint32_t n_links, int32_t *proof_status, int32_t *receipt, uint32_t n,
+                    void *stream);
 
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from

@@ -39,6 +39,12 @@ Transport.packet_filter between unpack and dispatch (Transport.py:1377-1427,
 Announces: ``pipeline.inbound(..., announces=True)`` validates every announce
 of a read inside its packet (Identity.validate_announce, Identity.py:505-606;
 ``device.announce_validate`` is the stage alone).
+Packet proofs on links (``reticulum_amd.proof``): ``LinkSigners`` (the links'
+signing rows) and ``ReceiptTable`` (Transport.receipts on the device);
+``pipeline.inbound(..., links=table, signers=s, receipts=t)`` proves the packets
+a link proves (Link.py:943-955, 1140-1145, 378-389) and settles the proofs that
+come back (Transport.py:2326-2363, Packet.py:434-459); ``device.link_prove`` and
+``device.proof_settle`` are the stages alone.
 
 ``available()`` tells whether the library and a gfx950 device are usable;
 ``reticulum_amd.dropin`` is the import for the reference's one-line swap,
@@ -58,6 +64,8 @@ from . import link  # noqa: F401
 from .link import LinkTable, derive_link_keys, link_id_from_lr_packet  # noqa: F401
 from . import filter  # noqa: F401
 from .filter import PacketHashlist  # noqa: F401
+from . import proof  # noqa: F401
+from .proof import LinkSigners, ReceiptTable  # noqa: F401
 from .token import AES, AES_128_CBC, AES_256_CBC, KeySet, Packed, Token, TOKEN_OVERHEAD, token_len  # noqa: F401
 
 __version__ = "0.1.0"

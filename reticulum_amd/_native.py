@@ -23,6 +23,9 @@ RT_FILTER_PASS, RT_FILTER_NO_PACKET, RT_FILTER_OTHER_TRANSPORT = 0, 1, 2
 RT_FILTER_BAD_ANNOUNCE, RT_FILTER_HOPS, RT_FILTER_DUPLICATE = 3, 4, 5
 RT_ANNOUNCE_VALID, RT_ANNOUNCE_NOT_ANNOUNCE, RT_ANNOUNCE_SHORT = 0, 1, 2
 RT_ANNOUNCE_BAD_SIGNATURE, RT_ANNOUNCE_BAD_DESTINATION = 3, 4
+RT_LINK_PROVE_ALL, RT_LINK_HAS_CHANNEL = 1, 2
+RT_PROOF_DELIVERED, RT_PROOF_NOT_PROOF, RT_PROOF_NOT_LINK, RT_PROOF_NO_LINK = 0, 1, 2, 3
+RT_PROOF_SHORT, RT_PROOF_NO_RECEIPT, RT_PROOF_BAD_SIGNATURE = 4, 5, 6
 # the RNSTOK_ABI_VERSION (include/rnstok.h) these bindings are written for;
 # load() refuses any other build of the library
 ABI_VERSION = 3
@@ -111,6 +114,9 @@ SIGNATURES = [
     ("rt_hashlist_remove_host", _int, [_vp, _vp, _u32, _vp]),
     ("rt_hashlist_contains_host", _int, [_vp, _vp, _u32, _vp]),
     ("rt_announce_validate", _int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("rt_link_prove", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp, _u32, _vp]),
+    ("rt_receipt_store", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    ("rt_proof_settle", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
     ("rt_packet_pack_headers", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("rt_device_alloc", _vp, [_vp, _u64]),
     ("rt_device_free", None, [_vp, _vp]),

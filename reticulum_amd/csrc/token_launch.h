@@ -295,6 +295,49 @@ uint64_t link_rebuild_workspace_bytes(uint32_t cap);
 hipError_t launch_link_rebuild(const LinkTab &t, void *workspace, uint64_t *report, uint32_t ticket, hipStream_t s);
 hipError_t launch_link_spans(const LinkSpanArgs &a, hipStream_t s);
 
+// Packet proofs on a link (proof_kernels.hip).  The signers' rows are indexed
+// by the link table's value: seeds and publics 32 bytes each at l*key_stride
+// (0: one row for every link), flags one byte each (1: the link proves every
+// packet it could decrypt, 2: it has a channel), peer_publics 32 bytes each.
+// `work` is prove_workspace_bytes(n) / settle_workspace_bytes(n) of device
+// memory the launch may use until it has run.
+struct ProveArgs {
+    const uint8_t *fields;         // n rt_packet_fields records
+    const uint8_t *route;
+    const int32_t *link;
+    const int32_t *status;         // the token status of the decrypt
+    const uint8_t *seeds, *publics;
+    uint64_t key_stride;
+    const uint8_t *flags;
+    uint32_t n_links;
+    uint8_t *proofs;               // 115 bytes at proofs + i*proof_stride where proof_len[i] is 115
+    uint64_t proof_stride;
+    uint32_t *proof_len;
+    uint32_t *work;
+    uint32_t n;
+};
+struct SettleArgs {
+    LinkTab t;                     // the receipts: hash[:16] -> id
+    const uint8_t *hashes;         // max_receipts x 32 B, by id
+    uint32_t max_receipts;
+    const uint8_t *pkt;
+    const uint64_t *pkt_off;
+    const uint8_t *fields;
+    const int32_t *link;
+    const uint8_t *peer_publics;
+    uint32_t n_links;
+    int32_t *status, *receipt;
+    uint32_t *work;
+    uint32_t n;
+};
+uint64_t prove_workspace_bytes(uint32_t n);
+uint64_t settle_workspace_bytes(uint32_t n);
+hipError_t launch_link_prove(const ProveArgs &a, hipStream_t s);
+hipError_t launch_proof_settle(const SettleArgs &a, hipStream_t s);
+// store[ids[i]] = hashes[i] (32 bytes) where status[i] is RT_LINK_OK and ids[i] < max_receipts
+hipError_t launch_receipt_store(uint8_t *store, uint32_t max_receipts, const uint8_t *hashes, const uint32_t *ids,
+                                const int32_t *status, uint32_t n, hipStream_t s);
+
 // Packet hash list and packet filter (filter_kernels.hip; the layout is
 // described there).  Two generations of slot words and 32-byte hashes; which
 // of them is the current one is a word in device memory that every kernel reads.

@@ -858,6 +858,112 @@ def announce_validate(pkt, pkt_off, fields, status, identity_hash=None, stream=N
                                            _p(identity_hash), _stream(stream, pkt.device)))
 
 
+# Packet proofs on a link (proof_kernels.hip): ``signers`` is a
+# reticulum_amd.proof.LinkSigners (or anything with its seeds, publics,
+# peer_publics, flags and n_links), ``receipts`` a reticulum_amd.proof.ReceiptTable.
+
+LINK_PROVE_ALL, LINK_HAS_CHANNEL = 1, 2                                 # RT_LINK_* flags (include/rnstok.h)
+PROOF_DELIVERED, PROOF_NOT_PROOF, PROOF_NOT_LINK, PROOF_NO_LINK = 0, 1, 2, 3    # RT_PROOF_*
+PROOF_SHORT, PROOF_NO_RECEIPT, PROOF_BAD_SIGNATURE = 4, 5, 6
+PROOF_LEN = 115              # flags, hops, link id (16), context, packet hash (32), signature (64)
+
+
+def _check_fields(fields):
+    _check_u8(fields)
+    if fields.dim() != 2 or fields.shape[1] != 96 or not fields.is_contiguous():
+        raise ValueError("fields must be a contiguous (n, 96) uint8 tensor")
+    return fields.shape[0]
+
+
+def _same_device(dev, *ts):
+    for t in ts:
+        if t is not None and t.device != dev:
+            raise ValueError(f"every array must be on one device: {dev} and {t.device}")
+
+
+def link_prove(fields, route, link, status, signers, proofs, proof_len, stream=None):
+    """Link.receive's packet.prove() (Link.py:943-955, 1140-1145, 378-389) over
+    packet_unpack's records, link_spans' ``route`` ((n,) uint8) and ``link``
+    ((n,) int32) and the decrypt's token ``status`` ((n,) int32).  Record i is
+    proved when it is an ok DATA packet with 0 <= link[i] < signers.n_links and
+    either its context is NONE, its route ROUTE_LINK_DECRYPT, its token status
+    0 and the link's flags have LINK_PROVE_ALL, or its context is CHANNEL and
+    the flags have LINK_HAS_CHANNEL (whatever the token status).  Then
+    proof_len[i] ((n,) int32) = 115 and row i of ``proofs`` ((n, >=115) uint8 at
+    any row stride) is the LINK PROOF packet the reference sends: 0x0F, hops 0,
+    the link id, context 0, the packet hash and its signature under the link's
+    seed (ed25519_sign's, bit for bit).  Elsewhere proof_len[i] = 0 and the
+    row is not written.  Nothing is synchronised."""
+    n = _check_fields(fields)
+    _check_u8(route, proofs, signers.seeds, signers.publics, signers.flags)
+    if route.numel() != n or not route.is_contiguous():
+        raise ValueError(f"route must be a contiguous ({n},) uint8 tensor")
+    _check_i32(n, link=link, status=status, proof_len=proof_len)
+    if link is None or status is None or proof_len is None:
+        raise ValueError("link, status and proof_len are required")
+    _check_rows("proofs", proofs, n, PROOF_LEN)
+    n_links = int(signers.n_links)
+    sd, stride = _ed_rows("signers.seeds", signers.seeds, n_links, 32)
+    pk, pk_stride = _ed_rows("signers.publics", signers.publics, n_links, 32)
+    if pk_stride != stride:
+        raise ValueError("signers.seeds and signers.publics must have the same rows")
+    if signers.flags.numel() != n_links or not signers.flags.is_contiguous():
+        raise ValueError(f"signers.flags must be a contiguous ({n_links},) uint8 tensor")
+    _same_device(fields.device, route, link, status, proofs, proof_len, signers.seeds, signers.publics, signers.flags)
+    if n == 0:
+        return
+    _native.check(_native.load().rt_link_prove(_ctx_of(fields), _p(fields), _p(route), _p(link), _p(status), sd, pk,
+                                               stride, _p(signers.flags), n_links, _p_rows(proofs),
+                                               max(proofs.stride(0), PROOF_LEN), _p(proof_len), n,
+                                               _stream(stream, fields.device)))
+
+
+def receipt_store(receipts, hashes, ids, status, stream=None):
+    """The second half of ReceiptTable.add: receipts.hashes[ids[i]] = hashes[i]
+    ((n, 32) uint8) where the insert's status[i] is LINK_OK."""
+    n = _packet_hashes(hashes)
+    _check_i32(n, ids=ids, status=status)
+    if ids is None or status is None:
+        raise ValueError("ids and status are required")
+    _same_device(hashes.device, ids, status, receipts.hashes)
+    _native.check(_native.load().rt_receipt_store(receipts.handle, _p(receipts.hashes), receipts.max_receipts,
+                                                  _p(hashes), _p(ids), _p(status), n,
+                                                  _stream(stream, hashes.device)))
+
+
+def proof_settle(pkt, pkt_off, fields, link, signers, receipts, proof_status, receipt, stream=None):
+    """The receipts' branch of Transport.inbound's PROOF handling
+    (Transport.py:2326-2363, Packet.py:434-459) over packet_unpack's records,
+    each proof read inside its packet pkt[pkt_off[i]:], as if the packets came
+    one after another in index order.  ``link`` is link_spans' ((n,) int32),
+    ``signers.peer_publics`` the links' peer signing keys, ``receipts`` a
+    ReceiptTable.  proof_status[i] ((n,) int32) is PROOF_NOT_PROOF (not ok, no
+    PROOF, or context LRPROOF / RESOURCE_PRF), PROOF_NOT_LINK, PROOF_NO_LINK,
+    PROOF_SHORT (data under 96 bytes), PROOF_NO_RECEIPT (no receipt holds
+    data[:32], or a lower index of the batch delivered it),
+    PROOF_BAD_SIGNATURE, or PROOF_DELIVERED; receipt[i] ((n,) int32) is the
+    delivered receipt's id, which leaves the table inside the call, and -1
+    elsewhere.  Nothing is synchronised."""
+    n = _check_fields(fields)
+    _check_u8(pkt, signers.peer_publics)
+    if pkt.dim() != 1 or not pkt.is_cuda or not pkt.is_contiguous():
+        raise ValueError("pkt must be a flat contiguous uint8 buffer in device memory")
+    _check_i64(n, pkt_off=pkt_off)
+    _check_i32(n, link=link, proof_status=proof_status, receipt=receipt)
+    if pkt_off is None or link is None or proof_status is None or receipt is None:
+        raise ValueError("pkt_off, link, proof_status and receipt are required")
+    n_links = int(signers.n_links)
+    pp = signers.peer_publics
+    if pp.dim() != 2 or pp.shape != (n_links, 32) or not pp.is_contiguous():
+        raise ValueError(f"signers.peer_publics must be a contiguous ({n_links}, 32) uint8 tensor")
+    _same_device(pkt.device, pkt_off, fields, link, proof_status, receipt, pp, receipts.hashes)
+    if n == 0:
+        return
+    _native.check(_native.load().rt_proof_settle(receipts.handle, _p(receipts.hashes), receipts.max_receipts, _p(pkt),
+                                                 _p(pkt_off), _p(fields), _p(link), _p(pp), n_links, _p(proof_status),
+                                                 _p(receipt), n, _stream(stream, pkt.device)))
+
+
 def ifac_mask(pkt, pkt_off, pkt_len, ifac, ifac_key, out, out_off, stream=None):
     """Transport.transmit's IFAC step (Transport.py:1069-1101): packet i plus
     its access code ifac[i] (n, ifac_size) -> pkt_len[i] + ifac_size masked

@@ -18,7 +18,10 @@ Inbound, as the interface's read loop hands frames to Transport:
     packet filter            Transport.py:1377-1427, 1525-1545 (with seen)
     announce validation      Identity.py:505-606, Transport.py:1748-1750, 1772
                              (with announces)
+    proofs settled           Transport.py:2326-2363, Packet.py:434-459 (with
+                             receipts, after the link dispatch)
     Token.decrypt            Token.py:100-114 (Link/Identity.decrypt)
+    packets proved           Link.py:943-955, 1140-1145, 378-389 (with signers)
 
 Every stage is one of reticulum_amd.device's kernels, the rearranging of
 offsets and lengths between them included (frames_compact, token_spans), and
@@ -128,7 +131,8 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
 
 
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
-            check_ifac=False, links=None, seen=None, transport_identity=None, transit=None, announces=False):
+            check_ifac=False, links=None, seen=None, transport_identity=None, transit=None, announces=False,
+            signers=None, receipts=None):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -212,9 +216,33 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     and reads ANNOUNCE_NOT_ANNOUNCE like every frame that is no announce.
     Spans, link dispatch and decrypt are untouched.  Blackholed identities, the
     known-destination key check, Identity.remember, ratchets and ingress
-    limiting stay with the caller, keyed by ``announce_identity``."""
+    limiting stay with the caller, keyed by ``announce_identity``.
+
+    ``signers`` (a :class:`reticulum_amd.proof.LinkSigners`, row l for the link
+    whose table value is l) and ``receipts`` (a
+    :class:`reticulum_amd.proof.ReceiptTable`), with ``links``, handle the
+    packet proofs of the read: ``signers`` alone proves, ``receipts`` beside it
+    (the proofs are verified under the signers' ``peer_publics``; a node that
+    proves nothing gives its links flags 0) also settles.  With ``receipts`` the
+    proofs that arrive are settled after the link dispatch
+    (device.proof_settle; Transport.py:2326-2363, Packet.py:434-459): the
+    result gains ``proof_status`` (int32 per frame, device.PROOF_*) and
+    ``receipt`` (int32: the delivered receipt's id, which has left the table,
+    or -1).  With ``signers`` the packets a link proves are proved after the
+    decrypt (device.link_prove; Link.py:943-955, 1140-1145, 378-389): the
+    result gains ``proofs`` (uint8, max_pairs x 128: the 115-byte LINK PROOF
+    packet where ``proof_len`` is 115) and ``proof_len`` (int32 per frame, 115
+    or 0).  A packet an earlier stage dropped is neither proved nor settled.
+    The proof rows are raw packets: compacting them by ``proof_len`` and
+    sending them (ifac_sign, ifac_mask, hdlc_frame) is the caller's part, and
+    so are links that prove by callback (PROVE_APP: flags 0, the caller signs
+    the ``packet_hash`` column of ``fields`` with device.ed25519_sign)."""
     if seen is not None and transport_identity is None:
         raise ValueError("seen needs transport_identity, the node's 16-byte transport id")
+    if (signers is not None or receipts is not None) and links is None:
+        raise ValueError("signers and receipts need links, the table that finds each packet's link")
+    if receipts is not None and signers is None:
+        raise ValueError("receipts needs signers: a proof is verified under its link's peer_publics row")
     if aligned is None:
         aligned = device.LINE * (max_pairs + 1) <= buf.numel()
     if check_ifac and ifac_size:
@@ -280,6 +308,10 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
             route = torch.empty(max_pairs, dtype=torch.uint8, device=dev)
             device.link_spans(links.handle, fields, f_off, ks.n_keys, tok_off, tok_len, key_idx, link, route,
                               stream=stream)
+            if receipts is not None:
+                proof_status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+                receipt = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+                device.proof_settle(un, f_off, fields, link, signers, receipts, proof_status, receipt, stream=stream)
         else:
             device.token_spans(fields, f_off, tok_off, tok_len, stream=stream)
         pt = torch.empty_like(un)
@@ -288,6 +320,10 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
         # each plaintext (at most its token's length - 48 bytes) is written inside its own token's span
         pt_off = tok_off + pt_shift if pt_shift else tok_off
         device.decrypt(ks, un, tok_off, tok_len, pt, pt_off, pt_len, status, key_idx=key_idx, stream=stream)
+        if signers is not None:
+            proofs = torch.empty((max_pairs, device.LINE), dtype=torch.uint8, device=dev)
+            proof_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            device.link_prove(fields, route, link, status, signers, proofs, proof_len, stream=stream)
     res = {"pt": pt, "pt_off": pt_off, "pt_len": pt_len, "status": status, "ifac": ifac,
            "ifac_status": ifac_status, "fields": fields, "frame_pair": frame_pair, "n_frames": n_frames,
            "frame_status": d_st, "frame_len": d_len, "counts": counts}
@@ -297,6 +333,10 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
         res["filter_status"] = filter_status
     if announces:
         res.update(announce_status=announce_status, announce_identity=announce_identity)
+    if signers is not None:
+        res.update(proofs=proofs, proof_len=proof_len)
+    if receipts is not None:
+        res.update(proof_status=proof_status, receipt=receipt)
     return res
 
 
