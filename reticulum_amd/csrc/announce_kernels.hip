@@ -26,10 +26,8 @@
 //       signature is judged first, the destination hash only when it holds.
 // The list's order depends on the scheduling; results are scattered back by
 // index, so nothing the caller sees depends on it.
-#include "token_device.h"
-#include "token_launch.h"
+#include "table_device.h"
 #include "ed25519_device.h"
-#include "../../include/rnstok.h"
 
 namespace rnstok {
 
@@ -110,15 +108,8 @@ __global__ void __launch_bounds__(ANNOUNCE_THREADS) k_announce_select(const Anno
         a.status[i] = st;
         if (a.identity) st16(a.identity + 16ull * i, row);
     }
-    // every lane of the wave is here: the waves of a block are whole
-    const uint64_t mask = __ballot(cand);
-    if (mask) {
-        const uint32_t lane = threadIdx.x & 63u;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(a.work, (uint32_t)__popcll(mask));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (cand) a.work[LIST_AT + base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = i;
-    }
+    const uint32_t at = wave_reserve(a.work, cand);          // table_device.h
+    if (cand) a.work[LIST_AT + at] = i;
 }
 
 // One wave per SIMD with the overflow in AGPRs, as k_ed25519_verify has: the

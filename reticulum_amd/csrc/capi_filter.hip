@@ -15,42 +15,33 @@ struct rt_hashlist {
 
 namespace {
 
-using ListCall = TableCall<rt_hashlist>;
-
 int check_list(const rt_hashlist *list) {
     if (!list || !list->ctx || !list->l.st) return fail(RT_E_INVAL, "null hash list");
     return RT_OK;
 }
-int check_batch(uint32_t n, const char *who) {
-    if (n > LINK_MAX_BATCH) return fail(RT_E_INVAL, std::string(who) + ": at most 2^30 - 2 items per call");
-    return RT_OK;
-}
 
 int add_on(rt_hashlist *list, const uint8_t *hashes, uint32_t n, hipStream_t s) {
-    ListCall call(list, s);
-    RT_HIP(call.begin(), "hash list ordering");
-    int32_t *scratch = nullptr;
-    RT_HIP(rec_alloc(list->ctx, 4ull * n, (uint32_t **)&scratch, s), "hash list scratch");
-    const hipError_t e = launch_hashlist_add(list->l, hashes, scratch, n, s);
-    const hipError_t f = hipFreeAsync(scratch, s);
-    RT_HIP(e, "hash list add");
-    RT_HIP(f, "hash list scratch");
-    RT_HIP(call.end(), "hash list ordering");
-    return RT_OK;
+    return table_call(list, s, "hash list ordering", [&] {
+        int32_t *scratch = nullptr;
+        RT_HIP(rec_alloc(list->ctx, 4ull * n, (uint32_t **)&scratch, s), "hash list scratch");
+        const hipError_t e = launch_hashlist_add(list->l, hashes, scratch, n, s);
+        const hipError_t f = hipFreeAsync(scratch, s);
+        RT_HIP(e, "hash list add");
+        RT_HIP(f, "hash list scratch");
+        return RT_OK;
+    });
 }
 int remove_on(rt_hashlist *list, const uint8_t *hashes, int32_t *status, uint32_t n, hipStream_t s) {
-    ListCall call(list, s);
-    RT_HIP(call.begin(), "hash list ordering");
-    RT_HIP(launch_hashlist_remove(list->l, hashes, status, n, s), "hash list remove");
-    RT_HIP(call.end(), "hash list ordering");
-    return RT_OK;
+    return table_call(list, s, "hash list ordering", [&] {
+        RT_HIP(launch_hashlist_remove(list->l, hashes, status, n, s), "hash list remove");
+        return RT_OK;
+    });
 }
 int contains_on(rt_hashlist *list, const uint8_t *hashes, uint8_t *found_out, uint32_t n, hipStream_t s) {
-    ListCall call(list, s);
-    RT_HIP(call.begin(), "hash list ordering");
-    RT_HIP(launch_hashlist_contains(list->l, hashes, found_out, n, s), "hash list contains");
-    RT_HIP(call.end(), "hash list ordering");
-    return RT_OK;
+    return table_call(list, s, "hash list ordering", [&] {
+        RT_HIP(launch_hashlist_contains(list->l, hashes, found_out, n, s), "hash list contains");
+        return RT_OK;
+    });
 }
 
 }  // namespace
@@ -70,50 +61,17 @@ rt_hashlist *rt_hashlist_create(rt_ctx *c, uint32_t max_hashes) {
     hipSetDevice(c->device);
     rt_hashlist *list = new rt_hashlist();
     list->ctx = c;
-    // one allocation on the reclaim stream: two generations of slot words, their hashes, the state
-    const uint64_t bytes = 80ull * cap + sizeof(HashListState);
-    uint8_t *base = nullptr;
-    hipStream_t s = c->stream;
-    hipError_t e = hipEventCreateWithFlags(&list->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = rec_alloc(c, bytes, (uint32_t **)&base, s);
-    if (e != hipSuccess) {
-        fail(RT_E_NOMEM, std::string("hash list allocation failed: ") + hipGetErrorString(e));
-        if (list->done) hipEventDestroy(list->done);
-        delete list;
-        return nullptr;
-    }
-    HashList &l = list->l;
-    l.slots[0] = (uint64_t *)base;
-    l.slots[1] = (uint64_t *)(base + 8ull * cap);
-    l.hashes[0] = base + 16ull * cap;
-    l.hashes[1] = base + 48ull * cap;
-    l.st = (HashListState *)(base + 80ull * cap);
-    l.cap = cap;
-    l.max = max_hashes;
-    list->last = s;
-    // the slot words and the state; a hash is read only behind a FULL word
-    if ((e = hipMemsetAsync(l.slots[0], 0, 16ull * cap, s)) != hipSuccess ||
-        (e = hipMemsetAsync(l.st, 0, sizeof(HashListState), s)) != hipSuccess ||
-        (e = hipEventRecord(list->done, s)) != hipSuccess) {
-        hip_fail(e, "hash list setup");
-        hipFreeAsync(base, s);
-        hipEventDestroy(list->done);
-        delete list;
-        return nullptr;
-    }
+    // two generations of slot words, their hashes, the state
+    uint8_t *base = table_alloc(list, "hash list", 16ull * cap, 80ull * cap, sizeof(HashListState));
+    if (!base) return nullptr;
+    list->l = HashList{{(uint64_t *)base, (uint64_t *)(base + 8ull * cap)},
+                       {base + 16ull * cap, base + 48ull * cap},
+                       (HashListState *)(base + 80ull * cap), cap, max_hashes};
     return list;
 }
 
-// No synchronisation: the memory goes back on the reclaim stream after the
-// last call on the list.
 void rt_hashlist_destroy(rt_hashlist *list) {
-    if (!list) return;
-    rt_ctx *c = list->ctx;
-    hipSetDevice(c->device);
-    hipStreamWaitEvent(c->stream, list->done, 0);
-    hipFreeAsync(list->l.slots[0], c->stream);
-    hipEventDestroy(list->done);
-    delete list;
+    if (list) table_free(list, list->l.slots[0]);
 }
 
 uint32_t rt_hashlist_capacity(const rt_hashlist *list) { return list ? list->l.cap : 0; }
@@ -127,31 +85,28 @@ int rt_packet_filter(rt_hashlist *list, rt_linktable *transit, const uint8_t *tr
     if (n == 0) return RT_OK;
     if (!transport_identity || !fields || !status) return fail(RT_E_INVAL, "rt_packet_filter: null buffer");
     hipStream_t s = as_stream(stream);
-    ListCall call(list, s);
-    RT_HIP(call.begin(), "hash list ordering");
     FilterArgs a{list->l, LinkTab{}, transport_identity, (uint8_t *)fields, status, n};
-    if (transit) {
+    const auto launch = [&] {
+        RT_HIP(launch_packet_filter(a, s), "packet filter");
+        return RT_OK;
+    };
+    return table_call(list, s, "hash list ordering", [&] {
+        if (!transit) return launch();
         // the transit table is read like any lookup on it: in host order with its inserts and removes
-        TableCall<rt_linktable> reads(transit, s);
-        RT_HIP(reads.begin(), "link table ordering");
-        a.transit = transit->t;
-        RT_HIP(launch_packet_filter(a, s), "packet filter");
-        RT_HIP(reads.end(), "link table ordering");
-    } else {
-        RT_HIP(launch_packet_filter(a, s), "packet filter");
-    }
-    RT_HIP(call.end(), "hash list ordering");
-    return RT_OK;
+        return table_call(transit, s, "link table ordering", [&] {
+            a.transit = transit->t;
+            return launch();
+        });
+    });
 }
 
 int rt_hashlist_cull(rt_hashlist *list, void *stream) {
     RT_TRY(check_list(list));
     hipStream_t s = as_stream(stream);
-    ListCall call(list, s);
-    RT_HIP(call.begin(), "hash list ordering");
-    RT_HIP(launch_hashlist_cull(list->l, s), "hash list cull");
-    RT_HIP(call.end(), "hash list ordering");
-    return RT_OK;
+    return table_call(list, s, "hash list ordering", [&] {
+        RT_HIP(launch_hashlist_cull(list->l, s), "hash list cull");
+        return RT_OK;
+    });
 }
 
 int rt_hashlist_add(rt_hashlist *list, const uint8_t *hashes, uint32_t n, void *stream) {
@@ -182,11 +137,10 @@ int rt_hashlist_counts(rt_hashlist *list, uint32_t *out, void *stream) {
     RT_TRY(check_list(list));
     if (!out) return fail(RT_E_INVAL, "rt_hashlist_counts: null out");
     hipStream_t s = as_stream(stream);
-    ListCall call(list, s);
-    RT_HIP(call.begin(), "hash list ordering");
-    RT_HIP(launch_hashlist_counts(list->l, out, s), "hash list counts");
-    RT_HIP(call.end(), "hash list ordering");
-    return RT_OK;
+    return table_call(list, s, "hash list ordering", [&] {
+        RT_HIP(launch_hashlist_counts(list->l, out, s), "hash list counts");
+        return RT_OK;
+    });
 }
 
 int rt_hashlist_add_host(rt_hashlist *list, const uint8_t *hashes, uint32_t n) {

@@ -11,10 +11,6 @@ int check_table(const rt_linktable *tab) {
     if (!tab || !tab->ctx || !tab->t.slots) return fail(RT_E_INVAL, "null link table");
     return RT_OK;
 }
-int check_batch(uint32_t n, const char *who) {
-    if (n > LINK_MAX_BATCH) return fail(RT_E_INVAL, std::string(who) + ": at most 2^30 - 2 items per call");
-    return RT_OK;
-}
 
 // The mapped words the rebuilds report into, made with the context's first table.
 bool ensure_reports(rt_ctx *c) {
@@ -54,29 +50,26 @@ hipError_t reclaim(rt_linktable *tab, uint32_t n, hipStream_t s) {
 
 int insert_on(rt_linktable *tab, const uint8_t *ids, const uint32_t *values, int32_t *status, uint32_t n,
               hipStream_t s) {
-    TableCall<rt_linktable> call(tab, s);
-    RT_HIP(call.begin(), "link table ordering");
-    RT_HIP(reclaim(tab, n, s), "link table rebuild");
-    RT_HIP(launch_link_insert(tab->t, ids, values, status, n, s), "link insert");
-    tab->book.on_insert(n);
-    RT_HIP(call.end(), "link table ordering");
-    return RT_OK;
+    return table_call(tab, s, "link table ordering", [&] {
+        RT_HIP(reclaim(tab, n, s), "link table rebuild");
+        RT_HIP(launch_link_insert(tab->t, ids, values, status, n, s), "link insert");
+        tab->book.on_insert(n);
+        return RT_OK;
+    });
 }
 int remove_on(rt_linktable *tab, const uint8_t *ids, int32_t *status, uint32_t n, hipStream_t s) {
-    TableCall<rt_linktable> call(tab, s);
-    RT_HIP(call.begin(), "link table ordering");
-    RT_HIP(launch_link_remove(tab->t, ids, status, n, s), "link remove");
-    tab->book.on_remove(n);
-    RT_HIP(call.end(), "link table ordering");
-    return RT_OK;
+    return table_call(tab, s, "link table ordering", [&] {
+        RT_HIP(launch_link_remove(tab->t, ids, status, n, s), "link remove");
+        tab->book.on_remove(n);
+        return RT_OK;
+    });
 }
 int lookup_on(rt_linktable *tab, const uint8_t *ids, uint32_t *values_out, uint8_t *found_out, uint32_t n,
               hipStream_t s) {
-    TableCall<rt_linktable> call(tab, s);
-    RT_HIP(call.begin(), "link table ordering");
-    RT_HIP(launch_link_lookup(tab->t, ids, values_out, found_out, n, s), "link lookup");
-    RT_HIP(call.end(), "link table ordering");
-    return RT_OK;
+    return table_call(tab, s, "link table ordering", [&] {
+        RT_HIP(launch_link_lookup(tab->t, ids, values_out, found_out, n, s), "link lookup");
+        return RT_OK;
+    });
 }
 
 }  // namespace
@@ -105,46 +98,16 @@ rt_linktable *rt_linktable_create(rt_ctx *c, uint32_t max_links) {
         std::lock_guard<std::mutex> g(c->link_mu);
         tab->report = c->link_next++ % rt_ctx::LINK_REPORTS;
     }
-    // one allocation on the reclaim stream: slot words, ids, values, live count
-    const uint64_t bytes = 28ull * cap + 16;
-    uint8_t *base = nullptr;
-    hipStream_t s = c->stream;
-    hipError_t e = hipEventCreateWithFlags(&tab->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = rec_alloc(c, bytes, (uint32_t **)&base, s);
-    if (e != hipSuccess) {
-        fail(RT_E_NOMEM, std::string("link table allocation failed: ") + hipGetErrorString(e));
-        if (tab->done) hipEventDestroy(tab->done);
-        delete tab;
-        return nullptr;
-    }
-    tab->t.slots = (uint64_t *)base;
-    tab->t.ids = base + 8ull * cap;
-    tab->t.values = (uint32_t *)(base + 24ull * cap);
-    tab->t.live = (uint32_t *)(base + 28ull * cap);
-    tab->t.cap = cap;
-    tab->last = s;
-    // the slot words and the live count; ids and values are read only behind a FULL word
-    if ((e = hipMemsetAsync(tab->t.slots, 0, 8ull * cap, s)) != hipSuccess ||
-        (e = hipMemsetAsync(tab->t.live, 0, 16, s)) != hipSuccess || (e = hipEventRecord(tab->done, s)) != hipSuccess) {
-        hip_fail(e, "link table setup");
-        hipFreeAsync(base, s);
-        hipEventDestroy(tab->done);
-        delete tab;
-        return nullptr;
-    }
+    // slot words, ids, values, live count
+    uint8_t *base = table_alloc(tab, "link table", 8ull * cap, 28ull * cap, 16);
+    if (!base) return nullptr;
+    tab->t = LinkTab{(uint64_t *)base, base + 8ull * cap, (uint32_t *)(base + 24ull * cap),
+                     (uint32_t *)(base + 28ull * cap), cap};
     return tab;
 }
 
-// No synchronisation: the memory goes back on the reclaim stream after the
-// last call on the table.
 void rt_linktable_destroy(rt_linktable *tab) {
-    if (!tab) return;
-    rt_ctx *c = tab->ctx;
-    hipSetDevice(c->device);
-    hipStreamWaitEvent(c->stream, tab->done, 0);
-    hipFreeAsync(tab->t.slots, c->stream);
-    hipEventDestroy(tab->done);
-    delete tab;
+    if (tab) table_free(tab, tab->t.slots);
 }
 
 uint32_t rt_linktable_capacity(const rt_linktable *tab) { return tab ? tab->t.cap : 0; }
@@ -179,11 +142,10 @@ int rt_linktable_count(rt_linktable *tab, uint32_t *count_out, void *stream) {
     RT_TRY(check_table(tab));
     if (!count_out) return fail(RT_E_INVAL, "rt_linktable_count: null count_out");
     hipStream_t s = as_stream(stream);
-    TableCall<rt_linktable> call(tab, s);
-    RT_HIP(call.begin(), "link table ordering");
-    RT_HIP(hipMemcpyAsync(count_out, tab->t.live, 4, hipMemcpyDeviceToDevice, s), "link count");
-    RT_HIP(call.end(), "link table ordering");
-    return RT_OK;
+    return table_call(tab, s, "link table ordering", [&] {
+        RT_HIP(hipMemcpyAsync(count_out, tab->t.live, 4, hipMemcpyDeviceToDevice, s), "link count");
+        return RT_OK;
+    });
 }
 
 int rt_linktable_insert_host(rt_linktable *tab, const uint8_t *ids, const uint32_t *values, int32_t *status,
@@ -243,12 +205,11 @@ int rt_link_spans(rt_linktable *tab, const rt_packet_fields *fields, const uint6
     if (!fields || !pkt_off || !tok_off || !tok_len || !key_idx || !link || !route)
         return fail(RT_E_INVAL, "rt_link_spans: null buffer");
     hipStream_t s = as_stream(stream);
-    TableCall<rt_linktable> call(tab, s);
-    RT_HIP(call.begin(), "link table ordering");
-    LinkSpanArgs a{(const uint8_t *)fields, pkt_off, tab->t, n_keys, tok_off, tok_len, key_idx, link, route, n};
-    RT_HIP(launch_link_spans(a, s), "link spans");
-    RT_HIP(call.end(), "link table ordering");
-    return RT_OK;
+    const LinkSpanArgs a{(const uint8_t *)fields, pkt_off, tab->t, n_keys, tok_off, tok_len, key_idx, link, route, n};
+    return table_call(tab, s, "link table ordering", [&] {
+        RT_HIP(launch_link_spans(a, s), "link spans");
+        return RT_OK;
+    });
 }
 
 }  // extern "C"

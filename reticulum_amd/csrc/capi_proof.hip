@@ -47,11 +47,10 @@ int rt_receipt_store(rt_linktable *receipts, uint8_t *receipt_hashes, uint32_t m
     if (n == 0) return RT_OK;
     if (!receipt_hashes || !hashes || !ids || !status) return fail(RT_E_INVAL, "rt_receipt_store: null buffer");
     hipStream_t s = as_stream(stream);
-    TableCall<rt_linktable> call(receipts, s);
-    RT_HIP(call.begin(), "receipt table ordering");
-    RT_HIP(launch_receipt_store(receipt_hashes, max_receipts, hashes, ids, status, n, s), "receipt store");
-    RT_HIP(call.end(), "receipt table ordering");
-    return RT_OK;
+    return table_call(receipts, s, "receipt table ordering", [&] {
+        RT_HIP(launch_receipt_store(receipt_hashes, max_receipts, hashes, ids, status, n, s), "receipt store");
+        return RT_OK;
+    });
 }
 
 int rt_proof_settle(rt_linktable *receipts, const uint8_t *receipt_hashes, uint32_t max_receipts, const uint8_t *pkt,
@@ -66,20 +65,19 @@ int rt_proof_settle(rt_linktable *receipts, const uint8_t *receipt_hashes, uint3
     if (n_links && !peer_publics) return fail(RT_E_INVAL, "rt_proof_settle: null peer_publics");
     rt_ctx *c = receipts->ctx;
     hipStream_t s = as_stream(stream);
-    TableCall<rt_linktable> call(receipts, s);
-    RT_HIP(call.begin(), "receipt table ordering");
-    uint32_t *work = nullptr;
-    RT_HIP(rec_alloc(c, settle_workspace_bytes(n), &work, s), "proof workspace");
-    const SettleArgs a{receipts->t, receipt_hashes, max_receipts, pkt, pkt_off, (const uint8_t *)fields, link,
-                       peer_publics, n_links, proof_status, receipt, work, n};
-    const hipError_t e = launch_proof_settle(a, s);
-    const hipError_t f = hipFreeAsync(work, s);
-    RT_HIP(e, "proof settle");
-    RT_HIP(f, "proof workspace");
-    // every delivered receipt leaves the mark of a removal behind
-    receipts->book.on_remove(n);
-    RT_HIP(call.end(), "receipt table ordering");
-    return RT_OK;
+    return table_call(receipts, s, "receipt table ordering", [&] {
+        uint32_t *work = nullptr;
+        RT_HIP(rec_alloc(c, settle_workspace_bytes(n), &work, s), "proof workspace");
+        const SettleArgs a{receipts->t, receipt_hashes, max_receipts, pkt, pkt_off, (const uint8_t *)fields, link,
+                           peer_publics, n_links, proof_status, receipt, work, n};
+        const hipError_t e = launch_proof_settle(a, s);
+        const hipError_t f = hipFreeAsync(work, s);
+        RT_HIP(e, "proof settle");
+        RT_HIP(f, "proof workspace");
+        // every delivered receipt leaves the mark of a removal behind
+        receipts->book.on_remove(n);
+        return RT_OK;
+    });
 }
 
 }  // extern "C"

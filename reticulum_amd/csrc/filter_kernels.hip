@@ -8,36 +8,30 @@
 // the two sets are two generations of an open-addressing table in device
 // memory and the rules are a few compares, one lane per unpacked packet.
 //
-// Layout.  The slot word is the link table's
-// (table_device.h).  A packet hash is a SHA-256, so its own bytes pick the
-// slot: bytes 0..3 (little endian) the home slot, bytes 4..7 the tag, and all
-// 32 bytes are compared before a hit counts.  Slot s of a generation owns
-// hashes[s] (32 B).  HashListState.sel says which generation is the current
-// one; every kernel reads it, and the cull flips it on the device, so no call
-// ever brings a count back to the host.
+// Each generation is one of table_device.h's tables (layout, probe, claim and
+// remove are there): the key is the 32-byte packet hash, and
+// slot s of a generation owns hashes[s].  HashListState.sel says which
+// generation is the current one; every kernel reads it, and the cull flips it
+// on the device, so no call ever brings a count back to the host.
 //
-// Determinism.  A batch is filtered as if its packets came one after another
+// Its own rules.  A batch is filtered as if its packets came one after another
 // in index order.  Equal hashes imply equal type bits, destination hash and
 // context, so all copies of a hash take the same branch of the rules (but for
 // the transport id rule, which is decided before the list is touched).
 // k_filter_claim decides everything that does not depend on the other packets
 // of the batch; a packet that is to be remembered and is not yet in the
-// current generation claims the first free slot of its chain with a PENDING
-// word that carries its batch index, or lowers the index of the PENDING slot
-// its own hash already has (compared through the batch's records) with a
-// 64-bit atomic minimum.  k_filter_settle: the packet whose index a slot still
-// carries is the first of its hash; it passes, and enters the hash while the
-// generation has room.  k_filter_finish: the other copies are duplicates where
-// the hash was entered (a SINGLE announce, or a packet the list is not
-// consulted for, passes all the same).  Which free slot a hash lands in may
-// differ from run to run; statuses and later lookups do not.
+// current generation meets the other copies of its hash in one slot (claim(),
+// the batch's keys being the hashes in its records).  k_filter_settle: the
+// packet whose index a slot still carries is the first of its hash; it passes,
+// and enters the hash while the generation has room.  k_filter_finish: the
+// other copies are duplicates where the hash was entered (a SINGLE announce,
+// or a packet the list is not consulted for, passes all the same).
 //
 // A generation holds at most `max` entries.  A packet that would be remembered
 // in a full generation passes and adds one to the overflow count.  When the
 // new hashes of one batch outnumber the room left, the number entered is the
 // room, and which of them are entered is not specified.
 #include "table_device.h"
-#include "../../include/rnstok.h"
 
 namespace rnstok {
 
@@ -49,37 +43,6 @@ constexpr uint32_t DUP_IF_ENTERED = 1u << 30;
 constexpr uint32_t SLOT_BITS = DUP_IF_ENTERED - 1u;
 constexpr uint32_t PKT_ANNOUNCE = 1u, PKT_PROOF = 3u, DEST_SINGLE = 0u, DEST_GROUP = 1u, DEST_PLAIN = 2u;
 constexpr uint32_t HEADER_2 = 1u, CTX_KEEPALIVE = 0xFAu, CTX_LRPROOF = 0xFFu;
-
-struct H32 {
-    u32x4 lo, hi;
-};
-__device__ __forceinline__ H32 ld32(const uint8_t *p) { return H32{ld16(p), ld16(p + 16)}; }
-__device__ __forceinline__ void st32(uint8_t *p, const H32 &h) {
-    st16(p, h.lo);
-    st16(p + 16, h.hi);
-}
-__device__ __forceinline__ bool same32(const H32 &a, const H32 &b) { return same(a.lo, b.lo) && same(a.hi, b.hi); }
-
-struct Gen {
-    uint64_t *slots;
-    uint8_t *hashes;
-};
-__device__ __forceinline__ Gen gen_of(const HashList &l, uint32_t g) {
-    return g ? Gen{l.slots[1], l.hashes[1]} : Gen{l.slots[0], l.hashes[0]};
-}
-
-// Whether a settled entry with this hash is in the generation.  Plain loads:
-// for a generation no kernel beside this one writes.
-__device__ __forceinline__ uint32_t find(const Gen &g, uint32_t cap, const H32 &h) {
-    const uint32_t mask = cap - 1u;
-    for (uint32_t p = 0; p < cap; ++p) {
-        const uint32_t s = (h.lo.x + p) & mask;
-        const uint64_t w = g.slots[s];
-        if (w == W_EMPTY) return cap;
-        if (w_state(w) == ST_FULL && w_tag(w) == h.lo.y && same32(ld32(g.hashes + 32ull * s), h)) return s;
-    }
-    return cap;
-}
 
 // KEEPALIVE, RESOURCE_REQ, RESOURCE_PRF, RESOURCE, CACHE_REQUEST, CHANNEL
 // (Transport.py:1388-1393): contexts 0x01, 0x03, 0x05, 0x08, 0x0E and 0xFA.
@@ -131,7 +94,8 @@ __global__ __launch_bounds__(TABLE_THREADS) void k_filter_claim(FilterArgs a, co
         }
         // Transport.py:1537, 1542
         remember = !(ptype == PKT_PROOF && ctx == CTX_LRPROOF);
-        if (remember && a.transit.slots) remember = find(a.transit, u32x4{r[9], r[10], r[11], r[12]}) == a.transit.cap;
+        if (remember && a.transit.slots)
+            remember = find(view_of(a.transit), u32x4{r[9], r[10], r[11], r[12]}) == a.transit.cap;
         dup_passes = ptype == PKT_ANNOUNCE && dtype == DEST_SINGLE;
         dup_status = ptype == PKT_ANNOUNCE ? RT_FILTER_BAD_ANNOUNCE : RT_FILTER_DUPLICATE;
         base = a.fields;
@@ -140,63 +104,27 @@ __global__ __launch_bounds__(TABLE_THREADS) void k_filter_claim(FilterArgs a, co
         a.status[i] = RT_FILTER_PASS;
         return;
     }
-    const H32 h = ld32(hash_of<FILTER>(base, i));
-    const uint32_t cur = a.l.st->sel, cap = a.l.cap, mask = cap - 1u;
-    const Gen g = gen_of(a.l, cur);
+    const auto batch_hash = [base](uint32_t j) { return ld32(hash_of<FILTER>(base, j)); };
+    const H32 h = batch_hash(i);
+    const uint32_t cur = a.l.st->sel;
     // what a copy found present gets
     const int32_t seen = consult && !dup_passes ? dup_status : RT_FILTER_PASS;
-    if (seen != RT_FILTER_PASS && find(gen_of(a.l, cur ^ 1u), cap, h) != cap) {
+    if (seen != RT_FILTER_PASS && find(view_of(a.l, cur ^ 1u), h) != a.l.cap) {
         // the previous generation has it: dropped, and not moved to the current one
         a.status[i] = seen;
         a.fields[(uint64_t)REC_BYTES * i] = 0;
         return;
     }
     // the count does not move while this kernel runs (k_filter_settle adds to it)
-    const bool claim = remember && a.l.st->count[cur] < a.l.max;
+    const bool may_claim = remember && a.l.st->count[cur] < a.l.max;
     const uint32_t prov = PROVISIONAL | (seen != RT_FILTER_PASS ? DUP_IF_ENTERED : 0u);
-    const uint64_t mine = word(h.lo.y, ST_PENDING, i);
-    int32_t out = RT_FILTER_PASS;
-    bool done = false;
-    // Every failed compare-and-swap means another item took a slot for good,
-    // so the generation has no free slot after at most cap of them.
-    for (uint32_t attempt = 0; attempt <= cap && !done; ++attempt) {
-        uint32_t free_s = cap;
-        uint64_t free_w = 0;
-        for (uint32_t p = 0; p < cap; ++p) {
-            const uint32_t s = (h.lo.x + p) & mask;
-            const uint64_t w = slot_load(g.slots + s);
-            const uint32_t st = w_state(w);
-            if (w == W_EMPTY || st == ST_TOMB) {
-                if (free_s == cap) {
-                    free_s = s;
-                    free_w = w;
-                }
-                if (w == W_EMPTY) break;
-                continue;
-            }
-            if (w_tag(w) != h.lo.y) continue;
-            if (st == ST_FULL) {
-                if (same32(ld32(g.hashes + 32ull * s), h)) {               // present: nothing to enter
-                    out = seen;
-                    done = true;
-                    break;
-                }
-            } else if (claim && same32(ld32(hash_of<FILTER>(base, w_idx(w))), h)) {     // PENDING: a copy in this batch
-                slot_min(g.slots + s, mine);
-                out = (int32_t)(prov | s);
-                done = true;
-                break;
-            }
-        }
-        if (done || !claim || free_s == cap) break;
-        if (slot_cas(g.slots + free_s, free_w, mine)) {
-            out = (int32_t)(prov | free_s);
-            done = true;
-        }
-    }
-    // absent and no slot taken: it passes; if it was to be remembered, the
-    // generation is full (or its chain has no free slot)
-    if (!done && remember) add_one(&a.l.st->overflow);
+    const Claim c = claim(view_of(a.l, cur), h, i, may_claim, batch_hash);
+    // present: nothing to enter.  Absent and no slot taken: it passes; if it
+    // was to be remembered, the generation is full (or its chain has no free slot)
+    const int32_t out = c.kind == CLAIM_PRESENT ? seen
+                        : c.kind == CLAIM_MET   ? (int32_t)(prov | c.slot)
+                                                : RT_FILTER_PASS;
+    if (c.kind == CLAIM_NONE && remember) add_one(&a.l.st->overflow);
     a.status[i] = out;
     if (FILTER && out > 0) a.fields[(uint64_t)REC_BYTES * i] = 0;
 }
@@ -208,7 +136,7 @@ __global__ __launch_bounds__(TABLE_THREADS) void k_filter_settle(FilterArgs a, c
     const uint32_t i = blockIdx.x * TABLE_THREADS + threadIdx.x;
     if (FILTER) base = a.fields;
     const uint32_t cur = a.l.st->sel;
-    const Gen g = gen_of(a.l, cur);
+    const TabView g = view_of(a.l, cur);
     bool won = false;
     uint32_t s = 0;
     uint64_t w = 0;
@@ -219,24 +147,16 @@ __global__ __launch_bounds__(TABLE_THREADS) void k_filter_settle(FilterArgs a, c
     }
     // room is handed out a wave at a time: one add to the count, and one back
     // for the lanes that came too late
-    const uint64_t m = __ballot(won);
-    if (!m) return;
-    const uint32_t lane = (uint32_t)__lane_id(), first = (uint32_t)__builtin_ctzll(m), k = (uint32_t)__popcll(m);
-    uint32_t before = 0;
-    if (lane == first)
-        before = __hip_atomic_fetch_add(&a.l.st->count[cur], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    before = __shfl(before, (int)first);
-    const uint32_t room = before < a.l.max ? a.l.max - before : 0u;
-    if (lane == first && k > room) {
-        __hip_atomic_fetch_sub(&a.l.st->count[cur], k - room, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(&a.l.st->overflow, k - room, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const uint32_t at = wave_reserve(&a.l.st->count[cur], won);
+    const bool late = won && at >= a.l.max;
+    count_live(&a.l.st->count[cur], late, 0xFFFFFFFFu);
+    count_live(&a.l.st->overflow, late, 1u);
     if (!won) return;
-    if ((uint32_t)__popcll(m & ((1ull << lane) - 1ull)) < room) {
-        st32(g.hashes + 32ull * s, ld32(hash_of<FILTER>(base, i)));
+    if (!late) {
+        st32(g.keys + 32ull * s, ld32(hash_of<FILTER>(base, i)));
         slot_store(g.slots + s, word(w_tag(w), ST_FULL, IDX_MASK));
     } else {
-        slot_store(g.slots + s, W_TOMB);         // other chains of this batch may run through the slot
+        tombstone(g.slots + s);                  // other chains of this batch may run through the slot
     }
     a.status[i] = RT_FILTER_PASS;
 }
@@ -248,9 +168,8 @@ __global__ __launch_bounds__(TABLE_THREADS) void k_filter_finish(FilterArgs a) {
     if (i >= a.n) return;
     const uint32_t v = (uint32_t)a.status[i];
     if (!(v & PROVISIONAL)) return;
-    const Gen g = gen_of(a.l, a.l.st->sel);
     int32_t out = RT_FILTER_PASS;
-    if (w_state(g.slots[v & SLOT_BITS]) != ST_FULL) {
+    if (w_state(view_of(a.l).slots[v & SLOT_BITS]) != ST_FULL) {
         add_one(&a.l.st->overflow);              // the first copy found no room, nor does this one
     } else if (FILTER && (v & DUP_IF_ENTERED)) {
         const uint32_t ptype = a.fields[(uint64_t)REC_BYTES * i + 7];
@@ -260,50 +179,13 @@ __global__ __launch_bounds__(TABLE_THREADS) void k_filter_finish(FilterArgs a) {
     a.status[i] = out;
 }
 
-// Remove, as the link table's: the items that find their hash in the current
-// generation meet in its slot's index, and the lowest index reports it.
-__global__ __launch_bounds__(TABLE_THREADS) void k_hash_unclaim(HashList l, const uint8_t *hashes, int32_t *status,
-                                                                uint32_t n) {
-    const uint32_t i = blockIdx.x * TABLE_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const H32 h = ld32(hashes + 32ull * i);
-    const Gen g = gen_of(l, l.st->sel);
-    const uint32_t mask = l.cap - 1u;
-    int32_t st = RT_LINK_MISSING;
-    for (uint32_t p = 0; p < l.cap; ++p) {
-        const uint32_t s = (h.lo.x + p) & mask;
-        const uint64_t w = slot_load(g.slots + s);
-        if (w == W_EMPTY) break;
-        if (w_state(w) == ST_FULL && w_tag(w) == h.lo.y && same32(ld32(g.hashes + 32ull * s), h)) {
-            slot_min(g.slots + s, word(h.lo.y, ST_FULL, i));
-            st = (int32_t)(PROVISIONAL | s);
-            break;
-        }
-    }
-    status[i] = st;
-}
-__global__ __launch_bounds__(TABLE_THREADS) void k_hash_unsettle(HashList l, int32_t *status, uint32_t n) {
-    const uint32_t i = blockIdx.x * TABLE_THREADS + threadIdx.x;
-    const uint32_t cur = l.st->sel;
-    const Gen g = gen_of(l, cur);
-    bool won = false;
-    if (i < n && ((uint32_t)status[i] & PROVISIONAL)) {
-        const uint32_t s = (uint32_t)status[i] & ~PROVISIONAL;
-        const uint64_t w = slot_load(g.slots + s);
-        won = w_state(w) == ST_FULL && w_idx(w) == i;
-        if (won) slot_store(g.slots + s, W_TOMB);
-        status[i] = won ? RT_LINK_OK : RT_LINK_MISSING;
-    }
-    count_live(&l.st->count[cur], won, 0xFFFFFFFFu);         // minus one each
-}
-
 __global__ __launch_bounds__(TABLE_THREADS) void k_hash_contains(HashList l, const uint8_t *hashes, uint8_t *found_out,
                                                                  uint32_t n) {
     const uint32_t i = blockIdx.x * TABLE_THREADS + threadIdx.x;
     if (i >= n) return;
     const H32 h = ld32(hashes + 32ull * i);
     const uint32_t cur = l.st->sel;
-    found_out[i] = find(gen_of(l, cur), l.cap, h) != l.cap ? 1u : find(gen_of(l, cur ^ 1u), l.cap, h) != l.cap ? 2u : 0u;
+    found_out[i] = find(view_of(l, cur), h) != l.cap ? 1u : find(view_of(l, cur ^ 1u), h) != l.cap ? 2u : 0u;
 }
 
 // The cull (Transport.py:656-658), decided where the count is: the current
@@ -322,7 +204,7 @@ __global__ void k_hash_cull(HashList l) {
 __global__ __launch_bounds__(TABLE_THREADS) void k_hash_clear(HashList l) {
     const uint32_t s = blockIdx.x * TABLE_THREADS + threadIdx.x;
     if (s >= l.cap || !l.st->rotate) return;
-    gen_of(l, l.st->sel).slots[s] = W_EMPTY;
+    view_of(l).slots[s] = W_EMPTY;
 }
 
 __global__ void k_hash_counts(HashList l, uint32_t *out) {
@@ -353,12 +235,10 @@ hipError_t launch_hashlist_add(const HashList &l, const uint8_t *hashes, int32_t
     return launch_enter<false>(FilterArgs{l, LinkTab{}, nullptr, nullptr, scratch, n}, hashes, s);
 }
 
+// Remove, as the link table's, from the current generation.
 hipError_t launch_hashlist_remove(const HashList &l, const uint8_t *hashes, int32_t *status, uint32_t n,
                                   hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_hash_unclaim, table_grid(n), dim3(TABLE_THREADS), 0, s, l, hashes, status, n);
-    hipLaunchKernelGGL(k_hash_unsettle, table_grid(n), dim3(TABLE_THREADS), 0, s, l, status, n);
-    return hipGetLastError();
+    return launch_table_remove<H32>(l, hashes, status, n, s);
 }
 
 hipError_t launch_hashlist_contains(const HashList &l, const uint8_t *hashes, uint8_t *found_out, uint32_t n,

@@ -9,38 +9,15 @@
 // (k_token_spans) so that the decrypt gets its span and its key index from one
 // pass over the unpacked fields.
 //
-// Table layout.  A link id is a truncated SHA-256, so its
-// own bytes are the hash: bytes 0..3 (little endian) pick the home slot, bytes
-// 4..7 are the tag, and all 16 bytes are compared before a match counts.  Slot
-// s is one 64-bit word plus the entry it owns, ids[s] (16 B) and values[s]:
-//
-//   word = tag << 32 | state << 30 | index
-//   state EMPTY (word 0)   never used: a probe stops here
-//         TOMB             removed: a probe walks on, an insert may take it
-//         FULL             entry present; index is all ones when settled
-//         PENDING          claimed by an insert in flight; index = batch index
-//
-// A miss costs one 8-byte load per slot probed (an empty word, or a tag that
-// differs); the 16-byte id is fetched only behind a matching tag.
-//
-// Determinism.  Items of a batch run concurrently, but what they decide does
-// not depend on their order.  Insert is two kernels.  k_link_claim: an item
-// whose id is already present (FULL) is a duplicate; otherwise it claims the
-// first free slot of its chain by compare-and-swap with a PENDING word that
-// carries its batch index, and an item that meets a PENDING slot of its own id
-// (compared through the batch's ids) lowers that word's index to its own with
-// a 64-bit atomic minimum instead of claiming: all items of one id meet in one
-// slot and the lowest index stays.  k_link_settle: the item whose index the
-// slot still carries writes the entry and makes the slot FULL, the others are
-// duplicates.  Remove works alike on the index field of the FULL word.  Which
-// free slot an id lands in may differ from run to run; what is found does not.
-//
-// Slot words are read and written with agent-scope atomics inside the kernels
-// that change them (the XCDs' L2s are not coherent for plain accesses within a
-// kernel); the kernels that only look up use plain loads.  The word and its
-// helpers are in table_device.h, shared with the packet hash list.
+// The table is one of table_device.h's (layout, probe, claim and remove, and
+// why a batch's outcome does not depend on its lanes' order):
+// the key is the 16-byte link id, and slot s owns ids[s] and values[s].  Its
+// own rules.  Insert: an id present before the batch is RT_LINK_DUPLICATE, a
+// chain without a free slot RT_LINK_FULL (k_link_claim); of the items of one id
+// the lowest index writes the entry, the others are duplicates (k_link_settle).
+// Remove is the shared kernel pair.  The rebuild gathers the live entries,
+// zeroes the slot words and puts the entries back.
 #include "table_device.h"
-#include "../../include/rnstok.h"
 
 namespace rnstok {
 
@@ -52,7 +29,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_link_lookup(LinkTab t, const u
                                                               uint8_t *found_out, uint32_t n) {
     const uint32_t i = blockIdx.x * LINK_THREADS + threadIdx.x;
     if (i >= n) return;
-    const uint32_t s = find(t, ld16(ids + 16ull * i));
+    const uint32_t s = find(view_of(t), ld16(ids + 16ull * i));
     const bool hit = s != t.cap;
     values_out[i] = hit ? t.values[s] : 0xFFFFFFFFu;
     found_out[i] = hit ? 1u : 0u;
@@ -64,45 +41,11 @@ __global__ __launch_bounds__(LINK_THREADS) void k_link_claim(LinkTab t, const ui
                                                              uint32_t n) {
     const uint32_t i = blockIdx.x * LINK_THREADS + threadIdx.x;
     if (i >= n) return;
-    const u32x4 id = ld16(ids + 16ull * i);
-    const uint32_t mask = t.cap - 1u;
-    const uint64_t mine = word(id.y, ST_PENDING, i);
-    // Every failed compare-and-swap means another item took a slot for good,
-    // so the table is full after at most cap of them.
-    for (uint32_t attempt = 0; attempt <= t.cap; ++attempt) {
-        uint32_t free_s = t.cap;
-        uint64_t free_w = 0;
-        for (uint32_t p = 0; p < t.cap; ++p) {
-            const uint32_t s = (id.x + p) & mask;
-            const uint64_t w = slot_load(t.slots + s);
-            const uint32_t st = w_state(w);
-            if (w == W_EMPTY || st == ST_TOMB) {
-                if (free_s == t.cap) {
-                    free_s = s;
-                    free_w = w;
-                }
-                if (w == W_EMPTY) break;
-                continue;
-            }
-            if (w_tag(w) != id.y) continue;
-            if (st == ST_FULL) {
-                if (same(ld16(t.ids + 16ull * s), id)) {
-                    status[i] = RT_LINK_DUPLICATE;
-                    return;
-                }
-            } else if (same(ld16(ids + 16ull * w_idx(w)), id)) {     // PENDING: an item of this batch
-                slot_min(t.slots + s, mine);
-                status[i] = (int32_t)(PROVISIONAL | s);
-                return;
-            }
-        }
-        if (free_s == t.cap) break;
-        if (slot_cas(t.slots + free_s, free_w, mine)) {
-            status[i] = (int32_t)(PROVISIONAL | free_s);
-            return;
-        }
-    }
-    status[i] = RT_LINK_FULL;
+    const auto batch_id = [ids](uint32_t j) { return ld16(ids + 16ull * j); };
+    const Claim c = claim(view_of(t), batch_id(i), i, true, batch_id);
+    status[i] = c.kind == CLAIM_PRESENT ? RT_LINK_DUPLICATE
+                : c.kind == CLAIM_MET   ? (int32_t)(PROVISIONAL | c.slot)
+                                        : RT_LINK_FULL;
 }
 
 // Insert, second kernel: the lowest batch index that met in a slot owns it.
@@ -124,41 +67,6 @@ __global__ __launch_bounds__(LINK_THREADS) void k_link_settle(LinkTab t, const u
     count_live(t.live, won, 1u);
 }
 
-// Remove, first kernel: the items that find their id meet in its slot's index.
-__global__ __launch_bounds__(LINK_THREADS) void k_link_unclaim(LinkTab t, const uint8_t *ids, int32_t *status,
-                                                               uint32_t n) {
-    const uint32_t i = blockIdx.x * LINK_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const u32x4 id = ld16(ids + 16ull * i);
-    const uint32_t mask = t.cap - 1u;
-    int32_t st = RT_LINK_MISSING;
-    for (uint32_t p = 0; p < t.cap; ++p) {
-        const uint32_t s = (id.x + p) & mask;
-        const uint64_t w = slot_load(t.slots + s);
-        if (w == W_EMPTY) break;
-        if (w_state(w) == ST_FULL && w_tag(w) == id.y && same(ld16(t.ids + 16ull * s), id)) {
-            slot_min(t.slots + s, word(id.y, ST_FULL, i));
-            st = (int32_t)(PROVISIONAL | s);
-            break;
-        }
-    }
-    status[i] = st;
-}
-
-// Remove, second kernel: the lowest index leaves the mark of a removal.
-__global__ __launch_bounds__(LINK_THREADS) void k_link_unsettle(LinkTab t, int32_t *status, uint32_t n) {
-    const uint32_t i = blockIdx.x * LINK_THREADS + threadIdx.x;
-    bool won = false;
-    if (i < n && ((uint32_t)status[i] & PROVISIONAL)) {
-        const uint32_t s = (uint32_t)status[i] & ~PROVISIONAL;
-        const uint64_t w = slot_load(t.slots + s);
-        won = w_state(w) == ST_FULL && w_idx(w) == i;
-        if (won) slot_store(t.slots + s, W_TOMB);
-        status[i] = won ? RT_LINK_OK : RT_LINK_MISSING;
-    }
-    count_live(t.live, won, 0xFFFFFFFFu);        // minus one each
-}
-
 // Rebuild in place, three steps on the stream: the live entries go to a
 // temporary in any order (their ids are distinct), the slot words are zeroed
 // (hipMemsetAsync), and the entries are put back from an empty table.
@@ -166,15 +74,8 @@ __global__ __launch_bounds__(LINK_THREADS) void k_link_gather(LinkTab t, uint8_t
                                                               uint32_t *count) {
     const uint32_t s = blockIdx.x * LINK_THREADS + threadIdx.x;
     const bool full = s < t.cap && w_state(t.slots[s]) == ST_FULL;
-    const uint64_t m = __ballot(full);
-    if (!m) return;
-    const uint32_t lane = (uint32_t)__lane_id(), first = (uint32_t)__builtin_ctzll(m);
-    uint32_t base = 0;
-    if (lane == first)
-        base = __hip_atomic_fetch_add(count, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    base = __shfl(base, (int)first);
+    const uint32_t at = wave_reserve(count, full);
     if (full) {
-        const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
         st16(tmp_ids + 16ull * at, ld16(t.ids + 16ull * s));
         tmp_values[at] = t.values[s];
     }
@@ -224,7 +125,7 @@ __global__ __launch_bounds__(LINK_THREADS) void k_link_spans(LinkSpanArgs a) {
     uint32_t route = RT_ROUTE_NOT_LINK, off = 0, len = 0, key = 0;
     int32_t link = -1;
     if ((w0 & 0xFFu) == 1u && dtype == DEST_LINK && (ptype == PKT_DATA || ptype == PKT_PROOF)) {
-        const uint32_t s = find(a.t, u32x4{r[9], r[10], r[11], r[12]});
+        const uint32_t s = find(view_of(a.t), u32x4{r[9], r[10], r[11], r[12]});
         route = RT_ROUTE_NO_LINK;
         if (s != a.t.cap) {
             const uint32_t v = a.t.values[s];
@@ -265,10 +166,7 @@ hipError_t launch_link_insert(const LinkTab &t, const uint8_t *ids, const uint32
 }
 
 hipError_t launch_link_remove(const LinkTab &t, const uint8_t *ids, int32_t *status, uint32_t n, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_link_unclaim, grid_for(n), dim3(LINK_THREADS), 0, s, t, ids, status, n);
-    hipLaunchKernelGGL(k_link_unsettle, grid_for(n), dim3(LINK_THREADS), 0, s, t, status, n);
-    return hipGetLastError();
+    return launch_table_remove<u32x4>(t, ids, status, n, s);
 }
 
 uint64_t link_rebuild_workspace_bytes(uint32_t cap) { return 20ull * cap + 16; }

@@ -31,7 +31,7 @@
 //   k_settle_verify  one lane per candidate: verifies hash and signature where
 //       they lie in the packet (a 32-byte message).  A lane whose signature
 //       holds lowers the index field of the receipt's slot word to its record
-//       index (a 64-bit atomic minimum, as k_link_unclaim does): the lowest
+//       index (a 64-bit atomic minimum, table_device.h's full_lower): the lowest
 //       index that verified stays, whatever copies with bad signatures lie
 //       below it.
 //   k_settle_close   one lane per candidate: the record whose index the slot
@@ -41,12 +41,11 @@
 //       candidate of a receipt sees the same winner.
 //   k_settle_remove  the delivered records leave the mark of a removal.
 // Only the verify and the remove kernel write slot words, with
-// table_device.h's atomics.
+// table_device.h's removal steps (full_lower, tombstone).
 // The lists' order depends on the scheduling; results are scattered by record
 // index, so nothing the caller sees depends on it.
 #include "table_device.h"
 #include "ed25519_device.h"
-#include "../../include/rnstok.h"
 
 namespace rnstok {
 
@@ -63,16 +62,10 @@ constexpr uint32_t FLAG_PROVE_ALL = 1u, FLAG_HAS_CHANNEL = 2u;
 constexpr uint32_t LIST_AT = 16;
 
 // Appends the wave's candidates to the list: one ballot and one atomic add per
-// wave.  Every lane of the wave calls it (the waves of a block are whole).
+// wave (wave_reserve, table_device.h).
 __device__ __forceinline__ void append(uint32_t *work, bool cand, uint32_t i) {
-    const uint64_t mask = __ballot(cand);
-    if (mask) {
-        const uint32_t lane = threadIdx.x & 63u;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(work, (uint32_t)__popcll(mask));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (cand) work[LIST_AT + base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = i;
-    }
+    const uint32_t at = wave_reserve(work, cand);
+    if (cand) work[LIST_AT + at] = i;
 }
 
 __global__ void __launch_bounds__(PROOF_THREADS) k_prove_select(const ProveArgs a) {
@@ -139,7 +132,7 @@ __global__ void __launch_bounds__(PROOF_THREADS) k_settle_select(const SettleArg
             else {
                 st = RT_PROOF_NO_RECEIPT;
                 const uint8_t *h = a.pkt + a.pkt_off[i] + f.data_offset;
-                const uint32_t s = find(a.t, u32x4{le32(h), le32(h + 4), le32(h + 8), le32(h + 12)});
+                const uint32_t s = find(view_of(a.t), u32x4{le32(h), le32(h + 4), le32(h + 8), le32(h + 12)});
                 if (s != a.t.cap) {
                     const uint32_t v = a.t.values[s];
                     if (v < a.max_receipts) {
@@ -179,7 +172,7 @@ __global__ void __launch_bounds__(PROOF_THREADS) k_settle_verify(const SettleArg
     load_words(s, data + HASH + 32);
     if (ed25519_verify_words(pk, r, s, data, HASH)) {
         const uint32_t slot = a.work[LIST_AT + a.n + i];
-        slot_min(a.t.slots + slot, word(le32(data + 4), ST_FULL, i));
+        full_lower(a.t.slots + slot, le32(data + 4), i);
     } else {
         a.status[i] = RT_PROOF_BAD_SIGNATURE;
         a.receipt[i] = -1;
@@ -211,7 +204,7 @@ __global__ void __launch_bounds__(PROOF_THREADS) k_settle_remove(const SettleArg
     if (j < count) {
         const uint32_t i = a.work[LIST_AT + j];
         won = a.status[i] == RT_PROOF_DELIVERED;
-        if (won) slot_store(a.t.slots + a.work[LIST_AT + a.n + i], W_TOMB);
+        if (won) tombstone(a.t.slots + a.work[LIST_AT + a.n + i]);
     }
     count_live(a.t.live, won, 0xFFFFFFFFu);                     // minus one each
 }

@@ -185,6 +185,34 @@ def test_one_hash_twice_in_a_batch(variant):
     p.check()
 
 
+@pytest.mark.parametrize("n", [65, 257])
+def test_many_copies_inside_one_batch_lowest_index_wins(n):
+    """Five hashes with a dozen copies or more each, shuffled over one wave
+    plus a lane (65) and one workgroup plus a lane (257): each hash enters
+    once, and the filter passes the lowest index of each, every time."""
+    rng = np.random.Generator(np.random.PCG64(n))
+    d = 5
+    base = _hashes(rng, d)
+    for rep in range(3):
+        pick = np.arange(n) % d
+        rng.shuffle(pick)
+        pick[n - 1] = pick[0]            # first and last item: first wave and last workgroup
+        hs = [base[k] for k in pick]
+        assert len(set(hs)) == d
+        # through hashlist_add
+        p = Pair(4096)
+        p.lst.add(hs)
+        p.model.add(hs)
+        assert p.lst.counts() == p.model.counts() == (d, 0, 0)
+        assert p.lst.contains(base).cpu().tolist() == p.model.contains(base) == [1] * d
+        # through packet_filter (Pair.filter holds the statuses and the ok bytes to the model's)
+        p = Pair(4096)
+        want = p.filter([fh.packet(h) for h in hs])
+        assert want == [fh.PASS if hs.index(h) == i else fh.DUPLICATE for i, h in enumerate(hs)]
+        p.check()
+        assert p.model.counts() == (d, 0, 0)
+
+
 def test_previous_generation_only():
     rng = np.random.Generator(np.random.PCG64(656))
     p = Pair(8)
