@@ -48,16 +48,11 @@ __device__ __forceinline__ uint32_t be32(const uint8_t *p) {
     return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
 }
 
-__device__ __forceinline__ void sha256_iv(uint32_t h[8]) {
-    h[0] = 0x6a09e667u; h[1] = 0xbb67ae85u; h[2] = 0x3c6ef372u; h[3] = 0xa54ff53au;
-    h[4] = 0x510e527fu; h[5] = 0x9b05688cu; h[6] = 0x1f83d9abu; h[7] = 0x5be0cd19u;
-}
-
 // id = SHA-256(data[:64])[:16] (Identity.update_hashes) and
 // want = SHA-256(data[64:74] ‖ id)[:16] (Identity.py:563-564), as big-endian words
 __device__ void announce_hashes(uint32_t id[4], uint32_t want[4], const uint8_t *data) {
     uint32_t h[8], w[16];
-    sha256_iv(h);
+    sha256_init(h);
 #pragma unroll
     for (int k = 0; k < 16; ++k) w[k] = be32(data + 4 * k);
     sha256_compress(h, w);
@@ -69,7 +64,7 @@ __device__ void announce_hashes(uint32_t id[4], uint32_t want[4], const uint8_t 
 #pragma unroll
     for (int k = 0; k < 4; ++k) id[k] = h[k];
     // 26 bytes: the name hash, then the identity hash two bytes into word 2
-    sha256_iv(h);
+    sha256_init(h);
     w[0] = be32(data + KEYS);
     w[1] = be32(data + KEYS + 4);
     w[2] = ((uint32_t)data[KEYS + 8] << 24) | ((uint32_t)data[KEYS + 9] << 16) | (id[0] >> 16);

@@ -23,87 +23,36 @@ namespace rnstok {
 
 namespace {
 
-__device__ const uint32_t SHA_IV[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
-                                       0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+// Byte q of  pre (4 * npre bytes, put in as words by sha_msg) || seg || tail.
+// For q < skip, a byte of pre, q - skip wraps past seg_len and `tail` comes
+// back: no load, and sha_msg overwrites those words with pre.
+struct SegTailAt {
+    const uint8_t *seg;
+    uint32_t seg_len, skip, tail;
+    __device__ __forceinline__ uint32_t operator()(uint32_t q) const {
+        return q - skip < seg_len ? seg[q - skip] : tail;
+    }
+};
 
-// Byte q of  seg[0..seg_len) || tail (if tail >= 0) || 0x80 || zeros.
-__device__ __forceinline__ uint32_t msg_byte(const uint8_t *seg, uint32_t seg_len, int tail, uint32_t q) {
-    const uint32_t body = seg_len + (tail >= 0 ? 1u : 0u);
-    if (q < seg_len) return seg[q];
-    if (q < body) return (uint32_t)tail;
-    return q == body ? 0x80u : 0u;
-}
-
-// SHA-256 of  pre[0..npre) words || seg || tail  appended to `prior` bytes
-// already absorbed into h (prior = 64 after an HMAC ipad/opad block), with
-// the final padding.  npre is 0 or 8 (the previous HKDF block).
+// SHA-256 of  pre[0..npre) words || seg || tail (if tail >= 0)  appended to
+// `prior` bytes already absorbed into h (prior = 64 after an HMAC ipad/opad
+// block), with the final padding.  npre is 0 or 8 (the previous HKDF block).
 __device__ __forceinline__ void sha_msg(uint32_t h[8], uint32_t prior, const uint32_t pre[8], uint32_t npre,
                                      const uint8_t *seg, uint32_t seg_len, int tail) {
-    const uint64_t m = 4ull * npre + seg_len + (tail >= 0 ? 1u : 0u);
-    const uint64_t bits = (prior + m) * 8ull;
-    const uint64_t nblk = (m + 8u) / 64u + 1u;
-    for (uint64_t b = 0; b < nblk; ++b) {
+    // 32-bit like the byte index of the builder: seg_len is a context, salt or ikm length, far below 2^32
+    const uint32_t m = 4u * npre + seg_len + (tail >= 0 ? 1u : 0u);
+    const uint64_t bits = ((uint64_t)prior + m) * 8ull;
+    const uint32_t nblk = sha_pad_blocks(m);
+    for (uint32_t b = 0; b < nblk; ++b) {
         uint32_t w[16];
+        sha_pad_block(w, b, m, bits, SegTailAt{seg, seg_len, 4u * npre, (uint32_t)tail});
+        if (b == 0) {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (b == 0 && (uint32_t)k < npre) {
-                w[k] = pre[k];
-            } else {
-                const uint32_t q = (uint32_t)(64u * b + 4u * k) - 4u * npre;
-                w[k] = (msg_byte(seg, seg_len, tail, q) << 24) | (msg_byte(seg, seg_len, tail, q + 1) << 16) |
-                       (msg_byte(seg, seg_len, tail, q + 2) << 8) | msg_byte(seg, seg_len, tail, q + 3);
-            }
-        }
-        if (b + 1 == nblk) {
-            w[14] = (uint32_t)(bits >> 32);
-            w[15] = (uint32_t)bits;
+            for (int k = 0; k < 8; ++k)
+                if ((uint32_t)k < npre) w[k] = pre[k];
         }
         sha256_compress(h, w);
     }
-}
-
-// HMAC ipad / opad midstates for a key (HMAC.py:73-82).
-__device__ __forceinline__ void hmac_midstates(const uint32_t key[16], uint32_t hi[8], uint32_t ho[8]) {
-    uint32_t wi[16], wo[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        wi[i] = key[i] ^ 0x36363636u;
-        wo[i] = key[i] ^ 0x5c5c5c5cu;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hi[i] = ho[i] = SHA_IV[i];
-    sha256_compress(hi, wi);
-    sha256_compress(ho, wo);
-}
-
-// The same, one compression at a time (no interleaving of the two chains:
-// register pressure in k_hkdf_key_setup).
-__device__ __forceinline__ void hmac_midstates_serial(const uint32_t key[16], uint32_t hi[8], uint32_t ho[8]) {
-    uint32_t w[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) w[i] = key[i] ^ 0x36363636u;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hi[i] = ho[i] = SHA_IV[i];
-    sha256_compress_fenced(hi, w);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) w[i] = key[i] ^ 0x5c5c5c5cu;
-    sha256_compress_fenced(ho, w);
-}
-
-__device__ __forceinline__ void hmac_outer_fenced(uint32_t tag[8], const uint32_t inner[8], const uint32_t opad[8]) {
-    uint32_t w[16];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { w[i] = inner[i]; tag[i] = opad[i]; }
-    w[8] = 0x80000000u;
-#pragma unroll
-    for (int i = 9; i < 15; ++i) w[i] = 0;
-    w[15] = (64 + 32) * 8;
-    sha256_compress_fenced(tag, w);
-}
-
-// big-endian word at a 4-byte aligned address (FAST instance only)
-__device__ __forceinline__ uint32_t ld_be32(const uint8_t *p) {
-    return bswap(*(const uint32_t *)__builtin_assume_aligned(p, 4));
 }
 
 // HMAC(salt, .) ipad / opad midstates for key row i.
@@ -119,27 +68,14 @@ __device__ __forceinline__ void salt_midstates(const HkdfArgs &a, uint64_t i, ui
         for (int k = 0; k < 16; ++k) key[k] = 4u * k < sl ? ld_be32(salt + 4 * k) : 0u;
     } else if (sl > 64u) {                            // HMAC.py: long keys are hashed first
         uint32_t d[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) d[k] = SHA_IV[k];
+        sha256_init(d);
         sha_msg(d, 0u, nullptr, 0u, salt, sl, -1);
 #pragma unroll
         for (int k = 0; k < 16; ++k) key[k] = k < 8 ? d[k] : 0u;
     } else {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t q = 4u * k + j;
-                v = (v << 8) | (q < sl ? salt[q] : 0u);
-            }
-            key[k] = v;
-        }
+        hmac_key_words(key, salt, sl);
     }
-    if (FENCED)
-        hmac_midstates_serial(key, hi, ho);
-    else
-        hmac_midstates(key, hi, ho);
+    hmac_midstates<FENCED>(key, hi, ho);
 }
 
 // SHARED: one salt row for every key (salt_stride 0: a batch to one identity,
@@ -169,11 +105,7 @@ __global__ __launch_bounds__(256) void k_hkdf(HkdfArgs a) {
         for (int k = 0; k < 8; ++k) inner[k] = hi[k];
         if (FAST) {                                       // ikm_len % 4 == 0, ikm_len <= 52: one block
             uint32_t w[16];
-#pragma unroll
-            for (int k = 0; k < 14; ++k)
-                w[k] = 4u * k < a.ikm_len ? ld_be32(ikm + 4 * k) : (4u * k == a.ikm_len ? 0x80000000u : 0u);
-            w[14] = 0u;
-            w[15] = (64u + a.ikm_len) * 8u;
+            hkdf_prk_block(w, ikm, a.ikm_len);
             sha256_compress(inner, w);
         } else {
             sha_msg(inner, 64u, nullptr, 0u, ikm, a.ikm_len, -1);
@@ -189,19 +121,8 @@ __global__ __launch_bounds__(256) void k_hkdf(HkdfArgs a) {
             for (int k = 0; k < 8; ++k) inner[k] = hi[k];
             // T_blk = HMAC(PRK, T_{blk-1} || context || (blk+1) % 256)  (HKDF.py:56-60)
             if (FAST) {                                   // T_{blk-1} (32 B, none for blk 0) || counter byte
-                const uint32_t ctr = (((blk + 1u) & 255u) << 24) | 0x00800000u;
                 uint32_t w[16];
-#pragma unroll
-                for (int k = 0; k < 16; ++k) w[k] = 0u;
-                if (blk) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) w[k] = t[k];
-                    w[8] = ctr;
-                    w[15] = (64u + 33u) * 8u;
-                } else {
-                    w[0] = ctr;
-                    w[15] = (64u + 1u) * 8u;
-                }
+                hkdf_expand_block(w, t, blk);
                 sha256_compress(inner, w);
             } else {
                 sha_msg(inner, 64u, t, blk ? 8u : 0u, a.context, a.context_len, (int)((blk + 1u) & 255u));
@@ -260,44 +181,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const uint8_t *ikm = a.ikm + (uint64_t)i * a.ikm_stride;
         {
             uint32_t w[16];
-#pragma unroll
-            for (int k = 0; k < 14; ++k)
-                w[k] = 4u * k < a.ikm_len ? ld_be32(ikm + 4 * k) : (4u * k == a.ikm_len ? 0x80000000u : 0u);
-            w[14] = 0u;
-            w[15] = (64u + a.ikm_len) * 8u;
+            hkdf_prk_block(w, ikm, a.ikm_len);
 #pragma unroll
             for (int k = 0; k < 8; ++k) inner[k] = hi[k];
             sha256_compress_fenced(inner, w);
         }
-        hmac_outer_fenced(prk, inner, ho);                      // PRK = HMAC(salt, ikm)  (HKDF.py:51)
+        hmac_outer<true>(prk, inner, ho);                      // PRK = HMAC(salt, ikm)  (HKDF.py:51)
         {
             uint32_t key[16];
 #pragma unroll
             for (int k = 0; k < 16; ++k) key[k] = k < 8 ? prk[k] : 0u;
-            hmac_midstates_serial(key, hi, ho);
+            hmac_midstates<true>(key, hi, ho);
         }
         uint32_t t1[8], t2[8];
         {                                                // T1 = HMAC(PRK, 0x01)  (HKDF.py:56-60)
             uint32_t w[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) w[k] = 0u;
-            w[0] = 0x01800000u;
-            w[15] = (64u + 1u) * 8u;
+            hkdf_expand_block(w, nullptr, 0u);
 #pragma unroll
             for (int k = 0; k < 8; ++k) inner[k] = hi[k];
             sha256_compress_fenced(inner, w);
-            hmac_outer_fenced(t1, inner, ho);
+            hmac_outer<true>(t1, inner, ho);
         }
         if (NK == 8) {                                   // T2 = HMAC(PRK, T1 || 0x02)
             uint32_t w[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) w[k] = k < 8 ? t1[k] : 0u;
-            w[8] = 0x02800000u;
-            w[15] = (64u + 33u) * 8u;
+            hkdf_expand_block(w, t1, 1u);
 #pragma unroll
             for (int k = 0; k < 8; ++k) inner[k] = hi[k];
             sha256_compress_fenced(inner, w);
-            hmac_outer_fenced(t2, inner, ho);
+            hmac_outer<true>(t2, inner, ho);
         }
         // key = T1 || T2 (big-endian words): sk = key[:HALF], ek = key[HALF:]  (Token.py:61-70)
         uint32_t skw[16], ekw[NK];
@@ -311,12 +222,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
 }  // namespace
 
+// The shape the FAST instances take: no context, ikm (<= 52 B: PRK's message
+// is one block) and salt (<= 64 B) in whole aligned words.
+static bool hkdf_fast_shape(const HkdfArgs &a) {
+    const auto aligned4 = [](const uint8_t *p, uint64_t stride) { return (((uintptr_t)p | stride) & 3u) == 0; };
+    return a.context_len == 0 && a.ikm_len % 4u == 0 && a.ikm_len <= 52u && aligned4(a.ikm, a.ikm_stride) &&
+           (a.salt == nullptr || (a.salt_len % 4u == 0 && a.salt_len <= 64u && aligned4(a.salt, a.salt_stride)));
+}
+
 hipError_t launch_hkdf(const HkdfArgs &a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
     const uint32_t threads = 256;
-    const auto aligned4 = [](const uint8_t *p, uint64_t stride) { return (((uintptr_t)p | stride) & 3u) == 0; };
-    const bool fast = a.context_len == 0 && a.ikm_len % 4u == 0 && a.ikm_len <= 52u && aligned4(a.ikm, a.ikm_stride) &&
-                      (a.salt == nullptr || (a.salt_len % 4u == 0 && a.salt_len <= 64u && aligned4(a.salt, a.salt_stride)));
+    const bool fast = hkdf_fast_shape(a);
     // a shared salt row: 1024 x 256 lanes (4 waves per SIMD on 256 CUs), each
     // computing the salt's midstates once for its n / 262144 keys
     const bool shared = a.salt != nullptr && a.salt_stride == 0 && a.n > 1;
@@ -336,9 +253,7 @@ hipError_t launch_hkdf(const HkdfArgs &a, hipStream_t s) {
 constexpr uint64_t FUSED_BLOCKS_PER_CU = 3;   // 48 KiB of staging and 132 VGPRs: 3 workgroups of 4 waves per CU
 hipError_t launch_hkdf_key_setup(const HkdfArgs &a, const uint8_t *sbox, uint32_t *rec, int n_cu, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
-    const auto aligned4 = [](const uint8_t *p, uint64_t stride) { return (((uintptr_t)p | stride) & 3u) == 0; };
-    const bool fast = a.context_len == 0 && a.ikm_len % 4u == 0 && a.ikm_len <= 52u && aligned4(a.ikm, a.ikm_stride) &&
-                      (a.salt == nullptr || (a.salt_len % 4u == 0 && a.salt_len <= 64u && aligned4(a.salt, a.salt_stride)));
+    const bool fast = hkdf_fast_shape(a);
     if (!fast || (a.length != 64u && a.length != 32u)) return hipErrorNotSupported;
     const bool shared = a.salt != nullptr && a.salt_stride == 0 && a.n > 1;
     uint64_t blocks = ((uint64_t)a.n + 255u) / 256u;

@@ -53,19 +53,8 @@ __device__ __forceinline__ void key_record(const uint8_t *sb, const uint32_t ekw
     constexpr int NR = NK + 6, TOTAL = 4 * (NR + 1);
     // HMAC midstates first, so the 4*(NR+1) schedule words are not live
     // across the two compressions (k_hkdf_key_setup stays at 3 waves/SIMD).
-    // HMAC midstates (HMAC.py:73-82): sk zero-padded to 64 B, ^0x36 / ^0x5c
-    uint32_t bi[16], bo[16], hi[8], ho[8];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        bi[i] = skw[i] ^ 0x36363636u;
-        bo[i] = skw[i] ^ 0x5c5c5c5cu;
-    }
-    const uint32_t iv0[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
-                             0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hi[i] = ho[i] = iv0[i];
-    sha256_compress_fenced(hi, bi);
-    sha256_compress_fenced(ho, bo);
+    uint32_t hi[8], ho[8];
+    hmac_midstates<true>(skw, hi, ho);
     uint32_t w[TOTAL];
 #pragma unroll
     for (int i = 0; i < NK; ++i) w[i] = ekw[i];

@@ -25,17 +25,6 @@ namespace rnstok {
 
 namespace {
 
-__device__ const uint32_t SHA_IV0[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
-                                        0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-
-__device__ __forceinline__ uint32_t byte2(const uint8_t *a, uint32_t alen, const uint8_t *b, uint32_t blen,
-                                          uint32_t q) {
-    if (q < alen) return a[q];
-    q -= alen;
-    if (q < blen) return b[q];
-    return q == blen ? 0x80u : 0u;
-}
-
 __global__ __launch_bounds__(256) void k_map_hashes(MapArgs m) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= m.n_parts) return;
@@ -44,8 +33,7 @@ __global__ __launch_bounds__(256) void k_map_hashes(MapArgs m) {
     const uint32_t r = m.part_res ? m.part_res[j] : 0u;
     const uint8_t *S = m.salts + (uint64_t)r * m.salt_len;
     uint32_t h[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) h[k] = SHA_IV0[k];
+    sha256_init(h);
     const uint32_t full = len >> 6;
     for (uint32_t b = 0; b < full; ++b) {
         const uint8_t *B = P + 64ull * b;
@@ -57,21 +45,7 @@ __global__ __launch_bounds__(256) void k_map_hashes(MapArgs m) {
     const uint32_t rem = len - 64u * full;
     const uint8_t *T = P + 64ull * full;
     const uint64_t bits = ((uint64_t)len + m.salt_len) * 8u;
-    const uint32_t tb = (rem + m.salt_len + 8u) / 64u + 1u;
-    for (uint32_t b = 0; b < tb; ++b) {
-        uint32_t w[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const uint32_t q = 64u * b + 4u * k;
-            w[k] = (byte2(T, rem, S, m.salt_len, q) << 24) | (byte2(T, rem, S, m.salt_len, q + 1) << 16) |
-                   (byte2(T, rem, S, m.salt_len, q + 2) << 8) | byte2(T, rem, S, m.salt_len, q + 3);
-        }
-        if (b + 1 == tb) {
-            w[14] = (uint32_t)(bits >> 32);
-            w[15] = (uint32_t)bits;
-        }
-        sha256_compress(h, w);
-    }
+    sha_tail(h, rem + m.salt_len, bits, Bytes2At{T, rem, S});
     // digest[:4] = big-endian first state word (MAPHASH_LEN = 4)
     const uint32_t d = bswap(h[0]);
     __builtin_memcpy(m.out + 4ull * j, &d, 4);
@@ -185,6 +159,8 @@ __device__ __forceinline__ void finish_suffix(uint32_t h[8], const uint32_t mid[
     }
 #pragma unroll
     for (int k = 0; k < 16; ++k) x[k] |= tw[k];
+    // rem + slen < 96: one or two blocks, in the form this site always had (with it k_resource_hashes is
+    // instruction for instruction what it was; sha256_device.h's sha_pad_blocks gives the same count)
     const uint32_t tb = (rem + slen + 8u) / 64u + 1u;
     const uint64_t bits = total * 8u;
 #pragma unroll
@@ -194,10 +170,7 @@ __device__ __forceinline__ void finish_suffix(uint32_t h[8], const uint32_t mid[
         uint32_t w[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) w[k] = b ? x[16 + k] : x[k];
-        if (b + 1u == tb) {
-            w[14] = (uint32_t)(bits >> 32);
-            w[15] = (uint32_t)bits;
-        }
+        if (b + 1u == tb) sha_put_bits(w, bits);
         sha256_compress_fenced(h, w);
     }
 }
@@ -259,8 +232,7 @@ __global__ __launch_bounds__(RES_HASH_THREADS) void k_resource_hashes(ResHashArg
     const uint8_t *P = a.data + a.seg_off[i];
     const uint32_t len = a.seg_len[i], full = len >> 6;
     uint32_t h[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) h[k] = SHA_IV0[k];
+    sha256_init(h);
     u32x4 b0, b1, b2, b3;
     if (full) { b0 = ld16(P); b1 = ld16(P + 16); b2 = ld16(P + 32); b3 = ld16(P + 48); }
     for (uint32_t b = 0; b < full; ++b) {
@@ -299,8 +271,10 @@ __global__ __launch_bounds__(128) void k_resource_hashes_split(ResHashArgs a) {
     const uint32_t len = a.seg_len[i], full = len >> 6;
     const uint32_t nchunks = (full + RES_SPLIT_CHUNK - 1u) / RES_SPLIT_CHUNK;
     uint32_t h[8];
+    // the shared initial state, read here and not through sha256_init: with the call inlined this kernel's
+    // prologue is scheduled otherwise and one segment of 1 MiB ran 0.1 % slower, outside the parent's spread
 #pragma unroll
-    for (int k = 0; k < 8; ++k) h[k] = SHA_IV0[k];
+    for (int k = 0; k < 8; ++k) h[k] = SHA256_IV[k];
     // step c: the producer expands chunk c while the consumer runs chunk c - 1
     for (uint32_t c = 0; c <= nchunks; ++c) {
         if (wave == 1u) {

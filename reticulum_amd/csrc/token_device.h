@@ -1,6 +1,7 @@
 // token_device.h — CDNA4 device primitives for the encrypted-token kernels.
 //
-// AES (FIPS-197) as T-table rounds over LDS, SHA-256 (FIPS 180-4) in VGPRs.
+// AES (FIPS-197) as T-table rounds over LDS; SHA-256 (FIPS 180-4) in VGPRs and
+// HMAC are sha256_device.h.
 // Reference semantics: RNS/Cryptography/aes/aes256.py:177-235 (block cipher,
 // CBC), RNS/Cryptography/HMAC.py:47-125 (HMAC), Token.py:87-114 (token).
 //
@@ -19,9 +20,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace rnstok {
+#include "sha256_device.h"
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+namespace rnstok {
 
 // Key record (u32 words), produced by k_key_setup:
 constexpr int REC_WORDS = 136;          // 544 B, 16-B aligned
@@ -44,21 +45,6 @@ template <int K> struct Sel {
 __device__ __forceinline__ uint32_t perm(uint32_t s, uint32_t lc, uint32_t sel) {
     return __builtin_amdgcn_perm(s, lc, sel);
 }
-
-// v_bitop3_b32 (gfx950): any 3-input bitwise function in ONE full-rate VALU op
-// (measured: tools/valu_peak.hip — v_bitop3 issues at the v_add/v_xor rate
-// while v_perm/v_alignbit/v_bfi/v_add3/v_and_or/SDWA issue at half rate).
-// Truth table index = {S0,S1,S2} bits, i.e. TT = f(0xF0, 0xCC, 0xAA).
-template <uint32_t TT>
-__device__ __forceinline__ uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_amdgcn_bitop3_b32(a, b, c, TT);
-}
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return bitop3<0x96>(a, b, c); }
-__device__ __forceinline__ uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) { return bitop3<0xE8>(a, b, c); }
-// (m & a) | (~m & b): SHA-256 Ch(e,f,g) and byte merges
-__device__ __forceinline__ uint32_t bfi(uint32_t m, uint32_t a, uint32_t b) { return bitop3<0xCA>(m, a, b); }
-// (a & m) | c
-__device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t m, uint32_t c) { return bitop3<0xEA>(a, m, c); }
 
 // LDS read at an absolute byte address of the workgroup's LDS (the table
 // image is the only LDS allocation and starts at 0, see fill_tables), so the
@@ -155,157 +141,6 @@ __device__ __forceinline__ uint32_t tlast_dec(uint32_t a, uint32_t b, uint32_t c
                                               const Lanes &L) {
     return bfi(0x0000ffffu, bfi(0x000000ffu, invs<0>(a, L), invs<1>(b, L)),
                bfi(0x00ff0000u, invs<2>(c, L), invs<3>(d, L))) ^ k;
-}
-
-// -------------------------------------------------------------- SHA-256 --
-
-__device__ __forceinline__ uint32_t rotr(uint32_t x, int n) { return __builtin_amdgcn_alignbit(x, x, n); }
-__device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
-
-// SHA-256 compression split into rounds so its VALU chain can be interleaved
-// with an AES chain (whose time is LDS latency) inside one wave.  The eight
-// working variables rotate through v[] by index instead of by moves:
-// at round i, a = v[(0-i)&7], b = v[(1-i)&7], ..., h = v[(7-i)&7].
-struct Sha256 {
-    uint32_t v[8];
-    uint32_t w[16];
-
-    __device__ __forceinline__ void start(const uint32_t h[8]) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = h[k];
-    }
-    __device__ __forceinline__ void round(int i) {
-        constexpr uint32_t K[64] = {
-            0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
-            0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
-            0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-            0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
-            0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-            0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-            0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
-            0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-        uint32_t wi;
-        if (i < 16) {
-            wi = w[i];
-        } else {
-            const uint32_t w15 = w[(i + 1) & 15], w2 = w[(i + 14) & 15];
-            const uint32_t s0 = xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3);
-            const uint32_t s1 = xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
-            wi = w[i & 15] = (w[i & 15] + s0 + w[(i + 9) & 15]) + s1;
-        }
-        const uint32_t a = v[(0 - i) & 7], b = v[(1 - i) & 7], c = v[(2 - i) & 7], d = v[(3 - i) & 7];
-        const uint32_t e = v[(4 - i) & 7], f = v[(5 - i) & 7], g = v[(6 - i) & 7], h = v[(7 - i) & 7];
-        const uint32_t t1 = (h + K[i] + wi) + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + bfi(e, f, g);
-        const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + maj3(a, b, c);
-        v[(3 - i) & 7] = d + t1;      // new e
-        v[(7 - i) & 7] = t1 + t2;     // new a
-    }
-    __device__ __forceinline__ void finish(uint32_t h[8]) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) h[k] += v[k];
-    }
-};
-
-__device__ __forceinline__ void sha256_compress(uint32_t h[8], const uint32_t w[16]) {
-    Sha256 S;
-    S.start(h);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) S.w[k] = w[k];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) S.round(i);
-    S.finish(h);
-}
-
-// The same with the scheduler fenced every 4 rounds: a message whose words
-// are all known up front otherwise has its whole schedule (W[16..63] + K)
-// hoisted ahead of the rounds, 64 live values; kernels that run many
-// compressions back to back at 3 waves/SIMD (k_hkdf_key_setup) spilled them.
-__device__ __forceinline__ void sha256_compress_fenced(uint32_t h[8], const uint32_t w[16]) {
-    Sha256 S;
-    S.start(h);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) S.w[k] = w[k];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {
-        S.round(i);
-        if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-    S.finish(h);
-}
-
-// SHA-256 message words from four 16-B units (big-endian words).
-__device__ __forceinline__ void sha_units(uint32_t w[16], u32x4 a, u32x4 b, u32x4 c, u32x4 d) {
-    w[0] = bswap(a.x); w[1] = bswap(a.y); w[2] = bswap(a.z); w[3] = bswap(a.w);
-    w[4] = bswap(b.x); w[5] = bswap(b.y); w[6] = bswap(b.z); w[7] = bswap(b.w);
-    w[8] = bswap(c.x); w[9] = bswap(c.y); w[10] = bswap(c.z); w[11] = bswap(c.w);
-    w[12] = bswap(d.x); w[13] = bswap(d.y); w[14] = bswap(d.z); w[15] = bswap(d.w);
-}
-
-// Final padded SHA block holding fu (0..3) 16-B units s0..s2 of the message,
-// then 0x80, zeros and the 64-bit big-endian bit length.
-__device__ __forceinline__ void sha_final_units(uint32_t h[8], uint32_t fu, u32x4 s0, u32x4 s1, u32x4 s2,
-                                                uint64_t bits) {
-    uint32_t w[16];
-    const u32x4 z = {0u, 0u, 0u, 0u};
-    sha_units(w, fu > 0 ? s0 : z, fu > 1 ? s1 : z, fu > 2 ? s2 : z, z);
-#pragma unroll
-    for (int k = 0; k < 16; k += 4) {
-        uint32_t hit = (uint32_t)(4 * fu) == (uint32_t)k ? 0x80000000u : 0u;
-        w[k] |= hit;
-    }
-    w[14] = (uint32_t)(bits >> 32);
-    w[15] |= (uint32_t)bits;
-    sha256_compress(h, w);
-}
-
-// HMAC outer hash: tag = SHA256(opad_state, inner_digest || pad), 96-byte message.
-__device__ __forceinline__ void hmac_outer(uint32_t tag[8], const uint32_t inner[8], const uint32_t opad[8]) {
-    uint32_t w[16];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { w[i] = inner[i]; tag[i] = opad[i]; }
-    w[8] = 0x80000000u;
-#pragma unroll
-    for (int i = 9; i < 15; ++i) w[i] = 0;
-    w[15] = (64 + 32) * 8;
-    sha256_compress(tag, w);
-}
-
-// The last compressions of an HMAC through ONE inlined sha256_compress, so a
-// kernel's packet loop carries a single copy of the 64 unrolled rounds:
-// k = first..2 runs the full block `blk` (k = 0), the final padded block `fin`
-// (k = 1) and the outer hash of the inner digest under the opad midstate
-// (k = 2).  h: the inner state in, the tag out.
-__device__ __forceinline__ void hmac_finish(uint32_t h[8], uint32_t first, const uint32_t blk[16],
-                                            const uint32_t fin[16], const uint32_t opad[8]) {
-#pragma nounroll
-    for (uint32_t k = first; k < 3u; ++k) {
-        uint32_t w[16];
-        if (k == 2u) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                w[j] = h[j];
-                h[j] = opad[j];
-            }
-            w[8] = 0x80000000u;
-#pragma unroll
-            for (int j = 9; j < 15; ++j) w[j] = 0u;
-            w[15] = (64u + 32u) * 8u;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) w[j] = k == 0u ? blk[j] : fin[j];
-        }
-        sha256_compress(h, w);
-    }
-}
-
-// Final padded block of an HMAC inner hash: the first fu (0..3) 16-B units of
-// u (big-endian words), 0x80, zeros, the 64-bit message length in bits.
-__device__ __forceinline__ void sha_final_block(uint32_t fin[16], const uint32_t u[16], uint32_t fu, uint64_t bits) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        fin[k] = (uint32_t)k < 4u * fu ? u[k] : ((uint32_t)k == 4u * fu ? 0x80000000u : 0u);
-    fin[14] = (uint32_t)(bits >> 32);
-    fin[15] = (uint32_t)bits;
 }
 
 // Generic byte-granular HMAC inner hash (rare lanes: malformed token lengths).

@@ -1526,31 +1526,6 @@ hipError_t launch_verify_trials(const TrialArgs &a, hipStream_t s) {
 // units and from byte loads otherwise.  No AES runs and nothing but the status
 // is written.
 
-// rem (< 64) message bytes at p, then 0x80, zeros and the 64-bit length
-// `bits`: the final one or two SHA-256 blocks, from byte loads.
-__device__ __forceinline__ void sha_tail_bytes(uint32_t h[8], const uint8_t *p, uint32_t rem, uint64_t bits) {
-    const uint32_t blocks = rem + 9u <= 64u ? 1u : 2u;
-#pragma nounroll
-    for (uint32_t b = 0; b < blocks; ++b) {
-        uint32_t w[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t q = 64u * b + 4u * k + j;
-                v = (v << 8) | (q < rem ? (uint32_t)p[q] : (q == rem ? 0x80u : 0u));
-            }
-            w[k] = v;
-        }
-        if (b + 1u == blocks) {
-            w[14] = (uint32_t)(bits >> 32);
-            w[15] = (uint32_t)bits;
-        }
-        sha256_compress(h, w);
-    }
-}
-
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_verify(VerifyArgs a) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
@@ -1577,7 +1552,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         const u32x4 z = {0u, 0u, 0u, 0u};
         sha_final_units(h, fu, fu > 0 ? ld16(R) : z, fu > 1 ? ld16(R + 16) : z, fu > 2 ? ld16(R + 32) : z, bits);
     } else {
-        sha_tail_bytes(h, R, rem, bits);
+        const uint32_t blocks = sha_pad_blocks(rem);  // the final one or two blocks, from byte loads
+#pragma nounroll
+        for (uint32_t b = 0; b < blocks; ++b) {
+            uint32_t w[16];
+            sha_pad_block(w, b, rem, bits, BytesAt{R});
+            sha256_compress(h, w);
+        }
     }
     load8(opad, r + REC_OPAD);
     hmac_outer(tag, h, opad);

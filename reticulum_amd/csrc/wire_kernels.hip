@@ -35,9 +35,6 @@ constexpr uint32_t HEADER_MINSIZE = 19, DST_LEN = 16, PATHFINDER_M = 128;
 constexpr uint32_t SCAN_BLOCK = 1024;
 constexpr uint32_t WAVE_GRID = 16384;        // workgroups of the wave-per-frame kernels (grid-stride beyond)
 
-__device__ const uint32_t SHA_IV[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
-                                       0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-
 // ------------------------------------------------------------------ scan --
 
 __device__ uint64_t block_exclusive_scan(uint64_t v, uint64_t *total) {
@@ -606,22 +603,9 @@ __global__ void k_deframe_counts(const uint64_t *nflags_p, const uint64_t *pos, 
 
 // HMAC midstates for a <= 64-byte key given as bytes
 __device__ __forceinline__ void key_midstates(const uint8_t *key, uint32_t klen, uint32_t hi[8], uint32_t ho[8]) {
-    uint32_t wi[16], wo[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t q = 4u * k + j;
-            v = (v << 8) | (q < klen ? key[q] : 0u);
-        }
-        wi[k] = v ^ 0x36363636u;
-        wo[k] = v ^ 0x5c5c5c5cu;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) hi[k] = ho[k] = SHA_IV[k];
-    sha256_compress(hi, wi);
-    sha256_compress(ho, wo);
+    uint32_t kw[16];
+    hmac_key_words(kw, key, klen);
+    hmac_midstates(kw, hi, ho);
 }
 
 // One lane per packet.  Outbound (MASK): new_raw = [raw0|0x80, raw1] || ifac ||
@@ -670,7 +654,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 4))) __launch_bounds__(256) voi
         // 4 % faster for the mask, 1.7 % slower for the unmask, whose early
         // exit makes the steps divergent (profiles/r03as_ifac_site_ab/)
         const uint64_t bits = (64ull + n) * 8ull;
-        const uint32_t nblk = (n + 8u) / 64u + 1u;
+        const uint32_t nblk = sha_pad_blocks(n);
         uint32_t st[8], prk[8];
 #pragma nounroll
         for (uint32_t s = 0; s < nblk + 3u; ++s) {
@@ -678,31 +662,14 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 4))) __launch_bounds__(256) voi
             if (s < nblk) {                       // PRK inner: ipad midstate, then the IFAC's blocks
 #pragma unroll
                 for (int k = 0; k < 8; ++k) h[k] = s == 0 ? key_ms[k] : st[k];
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint32_t q = 64u * s + 4u * k + j;
-                        v = (v << 8) | (q < n ? ifac[q] : (q == n ? 0x80u : 0u));
-                    }
-                    w[k] = v;
-                }
-                if (s + 1 == nblk) {
-                    w[14] = (uint32_t)(bits >> 32);
-                    w[15] = (uint32_t)bits;
-                }
+                sha_pad_block(w, s, n, bits, BytesAt{ifac});
             } else if (s == nblk) {               // PRK outer: opad midstate, inner digest
 #pragma unroll
-                for (int k = 0; k < 8; ++k) { h[k] = key_ms[8 + k]; w[k] = st[k]; }
-                w[8] = 0x80000000u;
-#pragma unroll
-                for (int k = 9; k < 15; ++k) w[k] = 0;
-                w[15] = (64 + 32) * 8;
+                for (int k = 0; k < 8; ++k) h[k] = key_ms[8 + k];
+                hmac_outer_block(w, st);
             } else {                              // PRK ^ ipad, PRK ^ opad
-                const uint32_t pad = s == nblk + 1u ? 0x36363636u : 0x5c5c5c5cu;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { h[k] = SHA_IV[k]; w[k] = prk[k] ^ pad; w[8 + k] = pad; }
+                sha256_init(h);
+                hmac_pad_block<8>(w, prk, s == nblk + 1u ? HMAC_IPAD : HMAC_OPAD);
             }
             sha256_compress(h, w);
 #pragma unroll
@@ -718,29 +685,11 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 4))) __launch_bounds__(256) voi
 #pragma unroll
         for (int k = 0; k < 8; ++k) { hi[k] = key_ms[k]; ho[k] = key_ms[8 + k]; }
         {
-            uint32_t w[16], h[8];
-            // ifac_size <= 64: one or two message blocks after the ipad block
-            const uint64_t bits = (64ull + n) * 8ull;
-            const uint32_t nblk = (n + 8u) / 64u + 1u;
+            uint32_t h[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) h[k] = hi[k];
-            for (uint32_t b = 0; b < nblk; ++b) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const uint32_t q = 64u * b + 4u * k + j;
-                        v = (v << 8) | (q < n ? ifac[q] : (q == n ? 0x80u : 0u));
-                    }
-                    w[k] = v;
-                }
-                if (b + 1 == nblk) {
-                    w[14] = (uint32_t)(bits >> 32);
-                    w[15] = (uint32_t)bits;
-                }
-                sha256_compress(h, w);
-            }
+            // ifac_size <= 64: one or two message blocks after the ipad block
+            sha_tail(h, n, (64ull + n) * 8ull, BytesAt{ifac});
             hmac_outer(prk, h, ho);
         }
         uint8_t prkb[32];
@@ -762,17 +711,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(4, 4))) __launch_bounds__(256) voi
     for (uint32_t b = 0; 32u * b < total; ++b) {
         // message T_{b-1} (32 B, none for b = 0) || counter byte
         uint32_t w[16], h[8];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) w[k] = 0;
-        if (b == 0) {
-            w[0] = ((b + 1u) & 255u) << 24 | 0x800000u;
-            w[15] = (64u + 1u) * 8u;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) w[k] = t[k];
-            w[8] = ((b + 1u) & 255u) << 24 | 0x800000u;
-            w[15] = (64u + 33u) * 8u;
-        }
+        hkdf_expand_block(w, t, b);
 #pragma unroll
         for (int k = 0; k < 8; ++k) h[k] = phi[k];
         sha256_compress(h, w);
@@ -905,8 +844,7 @@ __global__ __launch_bounds__(256) void k_token_spans(const rt_packet_fields *f, 
 // id's last byte) with `first` put in front, the last block(s) byte by byte.
 __device__ void sha_prefixed(uint8_t first, const uint8_t *src, uint32_t len, uint32_t out[8]) {
     uint32_t h[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) h[k] = SHA_IV[k];
+    sha256_init(h);
     const uint32_t m = len + 1u;
     const uint64_t bits = (uint64_t)m * 8u;
     const uint32_t nfull = m / 64u;
@@ -917,27 +855,8 @@ __device__ void sha_prefixed(uint8_t first, const uint8_t *src, uint32_t len, ui
         if (b == 0) w[0] = (w[0] & 0x00FFFFFFu) | ((uint32_t)first << 24);
         sha256_compress(h, w);
     }
-    const uint32_t r = m - 64u * nfull;                 // 0..63 message bytes left
-    const uint32_t nblk = (r + 8u) / 64u + 1u;
-    for (uint32_t bb = 0; bb < nblk; ++bb) {
-        uint32_t w[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t q = 64u * (nfull + bb) + 4u * k + j;
-                const uint32_t byte = q == 0 ? first : (q < m ? src[q - 1] : (q == m ? 0x80u : 0u));
-                v = (v << 8) | byte;
-            }
-            w[k] = v;
-        }
-        if (bb + 1 == nblk) {
-            w[14] = (uint32_t)(bits >> 32);
-            w[15] = (uint32_t)bits;
-        }
-        sha256_compress(h, w);
-    }
+    // the 0..63 message bytes left
+    sha_tail(h, m - 64u * nfull, bits, PrefixedAt{first, src, 64u * nfull});
 #pragma unroll
     for (int k = 0; k < 8; ++k) out[k] = h[k];
 }

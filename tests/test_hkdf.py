@@ -170,6 +170,89 @@ def test_gpu_hkdf_shared_salt_vs_oracle(salt_len, n):
     assert rc == 0 and np.array_equal(host, got)
 
 
+def _hkdf_ref(length, ikm, salt, context):
+    """HKDF.py:35-62 from hmac / hashlib alone."""
+    import hashlib
+    import hmac
+    prk = hmac.new(salt if salt else bytes(32), ikm, hashlib.sha256).digest()
+    okm, t = b"", b""
+    for i in range((length + 31) // 32):
+        t = hmac.new(prk, t + (context or b"") + bytes([(i + 1) % 256]), hashlib.sha256).digest()
+        okm += t
+    return okm[:length]
+
+
+# One length at a time moved onto the places where the last-block rule of a
+# SHA-256 message changes (55 / 56 bytes after the last whole block, a whole
+# block, one byte more), the others at the common shape (ikm 32, salt 16, no
+# context, 64 bytes out).  ikm: PRK's inner message after the ipad block.
+# salt: zero padded to a block, hashed first from 65 on (119 / 120: its own
+# last block).  context: T_1's message is context || 01 (54 -> 55 bytes, 55 ->
+# 56), T_2's is T_1 || context || 02 (22 -> 55, 23 -> 56).  Whole-word ikm up
+# to 52 bytes and whole-word salts up to 64 take the FAST instance, the others
+# the generic one; `shared` gives every row the one salt (stride 0).
+_EDGES = ([("ikm", v) for v in (51, 52, 53, 55, 56, 64, 119, 120)] +
+          [("salt", v) for v in (0, 1, 63, 64, 65, 119, 120)] +
+          [("context", v) for v in (54, 55, 22, 23)] +
+          [("length", v) for v in (1, 32, 33, 64, 65)] +
+          # a whole-word ikm of 52 bytes with a context: the generic instance at the FAST instance's limit
+          [("ikm52+context", 1)])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which,value,shared", [(w, v, s) for w, v in _EDGES for s in (False, True)
+                                                if not (s and (w, v) == ("salt", 0))])   # no salt row to share
+def test_gpu_hkdf_last_block_edges(which, value, shared):
+    import torch
+    from reticulum_amd import device
+    shape = {"ikm": 32, "salt": 16, "context": 0, "length": 64}
+    if which == "ikm52+context":
+        shape.update(ikm=52, context=value)
+    else:
+        shape[which] = value
+    n = 130                                        # three waves, the last one ragged
+    rng = np.random.Generator(np.random.PCG64(31 * value + len(which) + shared))
+    ikm = rng.integers(0, 256, (n, shape["ikm"]), dtype=np.uint8)
+    salt = rng.integers(0, 256, (1 if shared else n, shape["salt"]), dtype=np.uint8) if shape["salt"] else None
+    ctxb = rng.integers(0, 256, shape["context"], dtype=np.uint8).tobytes() if shape["context"] else None
+    out = torch.zeros((n, shape["length"]), dtype=torch.uint8, device="cuda")
+    st = None if salt is None else torch.from_numpy(salt).cuda()
+    if shared:
+        st = st.expand(n, shape["salt"])
+    device.hkdf(torch.from_numpy(ikm).cuda(), out, st,
+                None if ctxb is None else torch.frombuffer(bytearray(ctxb), dtype=torch.uint8).cuda())
+    got = out.cpu().numpy()
+    for i in range(n):
+        s = None if salt is None else salt[0 if shared else i].tobytes()
+        assert got[i].tobytes() == _hkdf_ref(shape["length"], ikm[i].tobytes(), s, ctxb), i
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shared", [False, True])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+@pytest.mark.parametrize("key_len", [64, 32])
+def test_gpu_derived_keyset_batch_edges(key_len, n, shared):
+    """The fused derive-and-key-setup kernel at one key, around a wave, and
+    over a workgroup: tokens under key i match the oracle under hkdf's key i."""
+    import torch
+    from reticulum_amd import device
+    rng = np.random.Generator(np.random.PCG64(key_len + 3 * n + shared))
+    L = 40
+    ikm = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    salt = rng.integers(0, 256, (1 if shared else n, 16), dtype=np.uint8)
+    st = torch.from_numpy(salt).cuda()
+    ks = device.derive_keyset(torch.from_numpy(ikm).cuda(), st.expand(n, 16) if shared else st, key_len=key_len)
+    pt = rng.integers(0, 256, (n, L), dtype=np.uint8)
+    iv = rng.integers(0, 256, (n, 16), dtype=np.uint8)
+    tok = torch.empty((n, rt.token_len(L)), dtype=torch.uint8, device="cuda")
+    kidx = torch.arange(n, dtype=torch.int32, device="cuda")
+    device.encrypt_uniform(ks, torch.from_numpy(pt).cuda(), L, torch.from_numpy(iv).cuda(), tok, key_idx=kidx)
+    th = tok.cpu().numpy()
+    for i in range(n):
+        key = _hkdf_ref(key_len, ikm[i].tobytes(), salt[0 if shared else i].tobytes(), None)
+        assert th[i].tobytes() == ctoken.encrypt(key, iv[i].tobytes(), pt[i].tobytes()), i
+
+
 @pytest.mark.gpu
 def test_gpu_hkdf_shared_salt_grid_stride():
     """600000 keys over the 1024 x 256-lane grid: lanes derive 2 or 3 keys."""

@@ -134,7 +134,7 @@ def random_parts(rng, lengths):
     return [rng.integers(0, 256, int(n), dtype=np.uint8).tobytes() for n in lengths]
 
 
-@pytest.mark.parametrize("salt_len", [0, 1, 4, 32, 55, 56, 60, 64, 130])
+@pytest.mark.parametrize("salt_len", [0, 1, 4, 32, 55, 56, 60, 63, 64, 119, 120, 130])
 def test_tail_blocks(salt_len):
     """Parts of every length 0..200 in neighbouring lanes, for two resources
     with salts of their own.  The tail is (rem + salt_len + 8) / 64 + 1 blocks

@@ -182,6 +182,30 @@ def test_gpu_ifac(wv):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("size", [1, 8, 16, 55, 56, 63, 64])
+def test_gpu_ifac_last_block_edges(size):
+    """The IFAC is the ikm of the mask's HKDF: after the ipad block its inner
+    hash takes one block up to 55 bytes and two from 56 on (63 / 64: the last
+    whole-block sizes).  Packets of every length 2..140 put the HKDF's output
+    length (packet + IFAC) on 31, 32, 33, 64 and 65 wherever the size leaves
+    room, and on every other place where a 32-byte block of the mask ends."""
+    from reticulum_amd import wire
+    rng = np.random.Generator(np.random.PCG64(5500 + size))
+    key = rng.integers(0, 256, 32, dtype=np.uint8).tobytes()
+    raws = [rng.integers(0, 128, 2, dtype=np.uint8).tobytes() + rng.integers(0, 256, n - 2, dtype=np.uint8).tobytes()
+            for n in range(2, 141)]
+    assert {len(r) + size for r in raws} >= {t for t in (31, 32, 33, 64, 65) if t >= size + 2} | {96, 97, 128, 129}
+    ifacs = [rng.integers(0, 256, size, dtype=np.uint8).tobytes() for _ in raws]
+    masked = wire.ifac_mask_batch(raws, ifacs, key)
+    assert masked == [ow.ifac_mask(r, f, key) for r, f in zip(raws, ifacs)]
+    got = wire.ifac_unmask_batch(masked, size, key)
+    assert got == [ow.ifac_unmask(m, size, key) for m in masked]
+    # item 0, the 2-byte packet, masks to 2 + size bytes, which inbound drops as too short (None above)
+    assert got[0] is None
+    assert [g[1] for g in got[1:]] == raws[1:] and [g[0] for g in got[1:]] == ifacs[1:]
+
+
+@pytest.mark.gpu
 def test_gpu_unpack_and_pack(wv):
     from reticulum_amd import wire
     raws = [b(r["raw"]) for r in wv["unpack"]]
@@ -208,6 +232,33 @@ def test_gpu_unpack_and_pack(wv):
         assert (g is None) == (o is None)
         if g:
             assert g == {k: o[k] for k in g}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("header_type", [0, 1])
+def test_gpu_unpack_hash_last_block_edges(header_type):
+    """The packet hash is over m = len - 1 (HEADER_1) or len - 17 (HEADER_2)
+    bytes.  Every m from the shortest packet to 300: m % 64 of 0, 1, 55, 56 and
+    63 at one, two, three and four whole blocks, for both header types."""
+    import hashlib
+    from reticulum_amd import wire
+    rng = np.random.Generator(np.random.PCG64(6600 + header_type))
+    cut = 17 if header_type else 1
+    shortest = 35 if header_type else 19
+    raws = []
+    for m in range(shortest - cut, 301):
+        raw = bytearray(rng.integers(0, 256, m + cut, dtype=np.uint8).tobytes())
+        raw[0] = (raw[0] & 0xBF) | (header_type << 6)
+        raw[1] &= 0x7F
+        raws.append(bytes(raw))
+    ms = {len(r) - cut for r in raws}
+    assert ms >= {64 * k + e for k in (1, 3) for e in (0, 1, 55, 56, 63)}
+    got = wire.unpack_batch(raws)
+    for raw, g in zip(raws, got):
+        assert g is not None and g["header_type"] == header_type
+        want = hashlib.sha256(bytes([raw[0] & 0x0F]) + raw[cut + 1:]).digest()
+        assert g["packet_hash"] == want, len(raw)
+        assert g == {k: ow.unpack(raw)[k] for k in g}
 
 
 @pytest.mark.gpu
