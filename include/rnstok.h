@@ -40,6 +40,9 @@
  *                                                RNS/Packet.py:199-200 (the proof packet)
  *   rt_receipt_store / Transport.receipts and     RNS/Transport.py:2326-2363 (the receipt of a link proof),
  *   rt_proof_settle    validate_link_proof        RNS/Packet.py:434-459
+ *   rt_link_accept     link requests answered      RNS/Transport.py:2127-2158, RNS/Destination.py:414-435,
+ *                      (responder side)            RNS/Link.py:186-227, 336-376, RNS/Packet.py:170-185
+ *   rt_keyset_set_rows_x25519  Link.handshake's key into a record of an existing key set  RNS/Link.py:348-361
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
@@ -815,6 +818,103 @@ int rt_proof_settle(rt_linktable *receipts, const uint8_t *receipt_hashes, uint3
                     const uint64_t *pkt_off, const rt_packet_fields *fields, const int32_t *link,
                     const uint8_t *peer_publics, uint32_t n_links, int32_t *proof_status, int32_t *receipt, uint32_t n,
                     void *stream);
+
+/* ---- link requests (Transport.py:2127-2158, Destination.py:414-435, Link.py:186-227, 336-376) */
+/* The responder side of link establishment for the node's own SINGLE
+ * destinations, over the n records rt_packet_unpack wrote (after
+ * rt_packet_filter where there is one: a dropped packet has ok = 0) and before
+ * rt_link_spans, so that the read's own packets on a new link find it.
+ *
+ * The destinations are an rt_linktable from 16-byte destination hash to a row
+ * 0 .. n_dests-1 of dest_seeds / dest_publics (32 bytes each: the identity's
+ * Ed25519 seed and rt_ed25519_public of it, trusted) and dest_flags (one byte:
+ * RT_DEST_ACCEPTS, accept_link_requests; RT_LINK_PROVE_ALL and
+ * RT_LINK_HAS_CHANNEL, which a new link's signer flags inherit).  nh_mtu is
+ * the receiving interface's next-hop MTU as Transport.py:2138-2141 computes it
+ * (HW_MTU when autoconfigured or fixed, else 500), or negative for an
+ * interface without HW_MTU.  status[i], the first rule that applies:
+ *   RT_LINKREQ_NOT_REQUEST      fields[i].ok == 0 or not a LINKREQUEST;
+ *   RT_LINKREQ_OTHER_TRANSPORT  HEADER_2 and the transport id is not
+ *                               transport_identity (16 bytes);
+ *   RT_LINKREQ_NO_DESTINATION   destination type not SINGLE, or the hash is not
+ *                               in `dests`;
+ *   RT_LINKREQ_NOT_ACCEPTING    the destination's RT_DEST_ACCEPTS is clear;
+ *   RT_LINKREQ_BAD_MODE         a path MTU (67 bytes of data, its 21-bit value
+ *                               not 0) above nh_mtu whose mode bits are not
+ *                               AES-256-CBC: the clamp's signalling_bytes raises;
+ *   RT_LINKREQ_BAD_SIZE         the data is neither 64 nor 67 bytes.  With a
+ *                               path MTU and no nh_mtu the three signalling
+ *                               bytes are cut off first (64 bytes, default mode
+ *                               and MTU), and the link id then covers them;
+ *   RT_LINKREQ_BAD_MODE         mode bits (data[64] >> 5 of 67 bytes) not 1;
+ *   RT_LINKREQ_NO_SLOT          valid request r in index order has no slot:
+ *                               r >= m, slots[r] not below n_keys and n_links,
+ *                               or the link table has no room;
+ *   RT_LINKREQ_DUPLICATE        its link id is in the link table already, or
+ *                               belongs to a request at a lower index that holds
+ *                               a slot: the lowest index wins whatever the
+ *                               scheduling, the duplicate's slot stays unused;
+ *   RT_LINKREQ_ACCEPTED         the link exists when the call has run.
+ * For every valid request (the last three) link_id[i] (n x 16) is the link id
+ * (Link.link_id_from_lr_packet on the packet as received) and mtu[i] the
+ * link's MTU (the path MTU clamped to nh_mtu, or 500); zeros elsewhere.  For an
+ * accepted one, with l = slots[r] = accepted[i] (-1 elsewhere):
+ *   - `links` maps link_id[i] to l (rt_linktable_insert's semantics);
+ *   - record l of `ks` (64-byte keys, l < rt_keyset_size) is Token(hkdf(64,
+ *     X25519(ephemeral[r], data[:32]), salt = link id)), Link.handshake's key
+ *     (data[:32] as a 256-bit value mod p, bit 255 not masked, as
+ *     X25519PrivateKey.exchange of the internal provider takes it),
+ *     where ephemeral (m x 32) is the caller's randomness for
+ *     X25519PrivateKey.generate, clamped by the ladder, row r for request r;
+ *   - proofs + i*proof_stride (proof_stride >= 118) holds the LRPROOF packet
+ *     Link.prove sends and proof_len[i] is 118 (0 elsewhere, row untouched):
+ *     0x0F, hops 0, link id, context 0xFF, then signature ‖ pub ‖ signalling
+ *     with pub = X25519(ephemeral[r], 9), signalling the three bytes of
+ *     Link.signalling_bytes(mtu, mode) and the signature rt_ed25519_sign's of
+ *     link id ‖ pub ‖ dest_publics[row] ‖ signalling under dest_seeds[row]
+ *     (fixed-base table; constant time in the seed and in ephemeral[r]);
+ *   - with sg_peer_publics given (n_links x 32) the signers' rows of l are
+ *     filled: sg_peer_publics[l] = data[32:64], sg_flags[l] = the destination's
+ *     flags & 3, and, where sg_stride is not 0, sg_seeds / sg_publics at
+ *     l*sg_stride = the destination's (sg_stride 0: one shared row, untouched).
+ * Neither shared secrets nor derived keys leave the device.  DEVICE pointers;
+ * the call only enqueues on the stream (its temporary comes from the context's
+ * stream-ordered pool) and takes its place in the host order of `links` and
+ * `dests`.  The key records are written in stream order: launches on this
+ * stream after the call see them, ordering other streams is the caller's part.
+ * n == 0 is RT_OK; n is at most 2^30 - 2. */
+#define RT_DEST_ACCEPTS 4u
+#define RT_LINKREQ_ACCEPTED        0
+#define RT_LINKREQ_NOT_REQUEST     1
+#define RT_LINKREQ_OTHER_TRANSPORT 2
+#define RT_LINKREQ_NO_DESTINATION  3
+#define RT_LINKREQ_NOT_ACCEPTING   4
+#define RT_LINKREQ_BAD_SIZE        6
+#define RT_LINKREQ_BAD_MODE        7
+#define RT_LINKREQ_DUPLICATE       8
+#define RT_LINKREQ_NO_SLOT         9
+int rt_link_accept(rt_linktable *links, rt_keyset *ks, rt_linktable *dests, const uint8_t *dest_seeds,
+                   const uint8_t *dest_publics, const uint8_t *dest_flags, uint32_t n_dests,
+                   const uint8_t *transport_identity, int64_t nh_mtu, const uint8_t *pkt, const uint64_t *pkt_off,
+                   const rt_packet_fields *fields, uint32_t n, const int32_t *slots, const uint8_t *ephemeral,
+                   uint32_t m, uint32_t n_links, uint8_t *sg_seeds, uint8_t *sg_publics, uint64_t sg_stride,
+                   uint8_t *sg_peer_publics, uint8_t *sg_flags, int32_t *status, int32_t *accepted, uint8_t *link_id,
+                   int32_t *mtu, uint8_t *proofs, uint64_t proof_stride, uint32_t *proof_len, void *stream);
+/* Records of an existing key set of 64-byte keys, rewritten on the device:
+ * for every item i of n that `mask` selects (mask[i] != 0; mask NULL: all)
+ * with rows[i] < rt_keyset_size, record rows[i] becomes Token(hkdf(64,
+ * X25519(scalar_i, point_i), salt_i)) (scalars, points, point_off and salt as
+ * rt_keyset_create_x25519, one salt row per item in whole aligned words, no
+ * context).  The selected rows are distinct.  Enqueued on `stream`, ordered
+ * after the key set's build: launches on that stream after the call read the
+ * new records, ordering other streams is the caller's part (the link table's
+ * rule), and rt_keyset_destroy still frees after it.  The exchange is
+ * rt_x25519's: bit 255 of a point is masked, where rt_link_accept takes a
+ * peer_pub's 256 bits mod p as they are (X25519PrivateKey.exchange). */
+int rt_keyset_set_rows_x25519(rt_keyset *ks, const uint8_t *scalars, uint64_t scalar_stride, const uint8_t *points,
+                              uint64_t point_stride, const uint64_t *point_off, const uint8_t *salt,
+                              uint64_t salt_stride, uint32_t salt_len, const uint32_t *rows, const uint8_t *mask,
+                              uint32_t n, void *stream);
 
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from

@@ -61,7 +61,7 @@ from .resource import build_hashmap, get_map_hash, resource_hashmap  # noqa: F40
 from .resource import prepare_resource, resource_hashes, validate_proof, verify_resource  # noqa: F401
 from . import wire  # noqa: F401
 from . import link  # noqa: F401
-from .link import LinkTable, derive_link_keys, link_id_from_lr_packet  # noqa: F401
+from .link import LinkDestinations, LinkTable, accept_requests_batch, derive_link_keys, link_id_from_lr_packet  # noqa: F401
 from . import filter  # noqa: F401
 from .filter import PacketHashlist  # noqa: F401
 from . import proof  # noqa: F401

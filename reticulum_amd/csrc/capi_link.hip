@@ -28,9 +28,11 @@ bool ensure_reports(rt_ctx *c) {
     return true;
 }
 
+}  // namespace
+
 // Before an insert of n items (table lock held): read the latest rebuild's
 // report if it has arrived, and enqueue a rebuild when the bound asks for one.
-hipError_t reclaim(rt_linktable *tab, uint32_t n, hipStream_t s) {
+hipError_t link_reclaim(rt_linktable *tab, uint32_t n, hipStream_t s) {
     rt_ctx *c = tab->ctx;
     LinkBook &b = tab->book;
     if (b.awaiting) {
@@ -48,10 +50,12 @@ hipError_t reclaim(rt_linktable *tab, uint32_t n, hipStream_t s) {
     return e != hipSuccess ? e : f;
 }
 
+namespace {
+
 int insert_on(rt_linktable *tab, const uint8_t *ids, const uint32_t *values, int32_t *status, uint32_t n,
               hipStream_t s) {
     return table_call(tab, s, "link table ordering", [&] {
-        RT_HIP(reclaim(tab, n, s), "link table rebuild");
+        RT_HIP(link_reclaim(tab, n, s), "link table rebuild");
         RT_HIP(launch_link_insert(tab->t, ids, values, status, n, s), "link insert");
         tab->book.on_insert(n);
         return RT_OK;

@@ -20,6 +20,10 @@ struct rt_linktable {
     uint32_t ticket = 0;           // of the latest rebuild enqueued
 };
 
+// Before an insert of n items, with the table's lock held: enqueues the rebuild
+// that reclaims removed slots when the table's book asks for one (capi_link.hip).
+hipError_t link_reclaim(rt_linktable *tab, uint32_t n, hipStream_t s);
+
 inline int check_batch(uint32_t n, const char *who) {
     if (n > LINK_MAX_BATCH) return fail(RT_E_INVAL, std::string(who) + ": at most 2^30 - 2 items per call");
     return RT_OK;

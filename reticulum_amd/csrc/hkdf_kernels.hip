@@ -154,13 +154,26 @@ __global__ __launch_bounds__(256) void k_hkdf(HkdfArgs a) {
 // the derived keys never reach HBM and one launch replaces two.  The loop is
 // wave-uniform (records are staged per wave); SHARED keeps the salt's
 // midstates for the lane's keys.
-template <bool SHARED, int NK>
+// ROWS (the link requests' stage and rt_keyset_set_rows_x25519; 64-byte keys,
+// one salt row per item): key i goes to record rows[i] of an existing table,
+// and with `count` only the first min(*count, a.n) items exist: the grid is
+// sized for a.n, and a workgroup past the count leaves its loop at once.
+template <bool ROWS>
+struct KeyRows {};
+template <>
+struct KeyRows<true> {
+    const uint32_t *rows, *count;
+};
+template <bool SHARED, int NK, bool ROWS = false>
 // 3 waves per SIMD: the 48 KiB staging area admits 3 workgroups per CU
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_hkdf_key_setup(HkdfArgs a, const uint8_t *sbox, uint32_t *rec_out) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_hkdf_key_setup(HkdfArgs a, const uint8_t *sbox, uint32_t *rec_out, KeyRows<ROWS> to) {
     __shared__ uint8_t sb[256];
     __shared__ u32x4 stage[4][KS_STAGE_PIECES];
     sb[threadIdx.x] = sbox[threadIdx.x];          // blockDim.x == 256
     __syncthreads();
+    if constexpr (ROWS) {
+        if (to.count && *to.count < a.n) a.n = *to.count;
+    }
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t shi[8], sho[8];
     if (SHARED) salt_midstates<true, true>(a, 0, shi, sho);
@@ -216,7 +229,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int k = 0; k < 16; ++k) skw[k] = k < (NK == 8 ? 8 : 4) ? t1[k] : 0u;
 #pragma unroll
         for (int k = 0; k < NK; ++k) ekw[k] = bswap(NK == 8 ? t2[k] : t1[4 + k]);
-        key_record<NK>(sb, ekw, skw, stage[wave], lane, kbase, a.n, rec_out);
+        if constexpr (ROWS)
+            key_record<NK, true>(sb, ekw, skw, stage[wave], lane, kbase, a.n, rec_out, to.rows);
+        else
+            key_record<NK>(sb, ekw, skw, stage[wave], lane, kbase, a.n, rec_out);
     }
 }
 
@@ -261,15 +277,25 @@ hipError_t launch_hkdf_key_setup(const HkdfArgs &a, const uint8_t *sbox, uint32_
     const dim3 grid((unsigned)blocks);
     if (a.length == 64u) {
         if (shared)
-            hipLaunchKernelGGL((k_hkdf_key_setup<true, 8>), grid, dim3(256), 0, s, a, sbox, rec);
+            hipLaunchKernelGGL((k_hkdf_key_setup<true, 8>), grid, dim3(256), 0, s, a, sbox, rec, KeyRows<false>{});
         else
-            hipLaunchKernelGGL((k_hkdf_key_setup<false, 8>), grid, dim3(256), 0, s, a, sbox, rec);
+            hipLaunchKernelGGL((k_hkdf_key_setup<false, 8>), grid, dim3(256), 0, s, a, sbox, rec, KeyRows<false>{});
     } else {
         if (shared)
-            hipLaunchKernelGGL((k_hkdf_key_setup<true, 4>), grid, dim3(256), 0, s, a, sbox, rec);
+            hipLaunchKernelGGL((k_hkdf_key_setup<true, 4>), grid, dim3(256), 0, s, a, sbox, rec, KeyRows<false>{});
         else
-            hipLaunchKernelGGL((k_hkdf_key_setup<false, 4>), grid, dim3(256), 0, s, a, sbox, rec);
+            hipLaunchKernelGGL((k_hkdf_key_setup<false, 4>), grid, dim3(256), 0, s, a, sbox, rec, KeyRows<false>{});
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_hkdf_key_setup_rows(const HkdfArgs &a, const uint8_t *sbox, uint32_t *rec, const uint32_t *rows,
+                                      const uint32_t *count, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    if (!hkdf_fast_shape(a) || a.length != 64u || (a.salt != nullptr && a.salt_stride == 0)) return hipErrorNotSupported;
+    const uint64_t blocks = ((uint64_t)a.n + 255u) / 256u;
+    hipLaunchKernelGGL((k_hkdf_key_setup<false, 8, true>), dim3((unsigned)blocks), dim3(256), 0, s, a, sbox, rec,
+                       KeyRows<true>{rows, count});
     return hipGetLastError();
 }
 

@@ -46,10 +46,14 @@ __device__ __forceinline__ void wave_lds_sync() {
 //   ekw: the AES key (key[HALF:]) as NK little-endian words
 //   skw: the HMAC key (key[:HALF]) as 16 big-endian words, zero padded
 //   sb:  the S-box in LDS;  st: this wave's KS_STAGE_PIECES staging pieces
-template <int NK>
+// ROWS: key kbase + r goes to record rows[kbase + r] instead of record
+// kbase + r, and nowhere where that is KS_NO_ROW (rows of an existing table,
+// rt_keyset_set_rows_x25519).
+constexpr uint32_t KS_NO_ROW = 0xFFFFFFFFu;
+template <int NK, bool ROWS = false>
 __device__ __forceinline__ void key_record(const uint8_t *sb, const uint32_t ekw[NK], const uint32_t skw[16],
                                           u32x4 *st, uint32_t lane, uint32_t kbase, uint32_t n_keys,
-                                          uint32_t *rec_out) {
+                                          uint32_t *rec_out, const uint32_t *rows = nullptr) {
     constexpr int NR = NK + 6, TOTAL = 4 * (NR + 1);
     // HMAC midstates first, so the 4*(NR+1) schedule words are not live
     // across the two compressions (k_hkdf_key_setup stays at 3 waves/SIMD).
@@ -105,7 +109,12 @@ __device__ __forceinline__ void key_record(const uint8_t *sb, const uint32_t ekw
         const uint32_t NP = (KS_PIECES - r * KS_P) < KS_P ? (KS_PIECES - r * KS_P) : KS_P;   // constant once unrolled
         for (uint32_t t = lane; t < nvalid * NP; t += 64u) {
             const uint32_t rr = t / NP, pc = t - rr * NP;
-            out[(uint64_t)(kbase + rr) * KS_PIECES + r * KS_P + pc] = st[rr * KS_P + pc];
+            if (ROWS) {
+                const uint32_t row = rows[kbase + rr];
+                if (row != KS_NO_ROW) out[(uint64_t)row * KS_PIECES + r * KS_P + pc] = st[rr * KS_P + pc];
+            } else {
+                out[(uint64_t)(kbase + rr) * KS_PIECES + r * KS_P + pc] = st[rr * KS_P + pc];
+            }
         }
         wave_lds_sync();
     }

@@ -338,6 +338,46 @@ hipError_t launch_proof_settle(const SettleArgs &a, hipStream_t s);
 hipError_t launch_receipt_store(uint8_t *store, uint32_t max_receipts, const uint8_t *hashes, const uint32_t *ids,
                                 const int32_t *status, uint32_t n, hipStream_t s);
 
+// Link requests (linkreq_kernels.hip): the records rt_packet_unpack wrote, the
+// node's destinations (a link table from destination hash to row, beside the
+// rows' seeds, publics and flags), the link table and key records the accepted
+// links go into, and the free list.  `work` is linkreq_workspace_bytes(n, m) of
+// device memory the launch may use until it has run.
+struct LinkReqArgs {
+    const uint8_t *pkt;
+    const uint64_t *pkt_off;
+    const uint8_t *fields;         // n rt_packet_fields records
+    const uint8_t *transport_id;   // 16 B
+    LinkTab dests;                 // destination hash -> row
+    const uint8_t *dest_seeds, *dest_publics;   // n_dests x 32 B each
+    const uint8_t *dest_flags;     // n_dests: RT_DEST_ACCEPTS | RT_LINK_PROVE_ALL | RT_LINK_HAS_CHANNEL
+    uint32_t n_dests;
+    uint32_t has_nh_mtu, nh_mtu;
+    LinkTab links;                 // link id -> slot
+    const int32_t *slots;          // m free slots, request r in stream order takes slots[r]
+    const uint8_t *ephemeral;      // m x 32 B, row r for request r
+    uint32_t m;
+    uint32_t n_keys, n_links;      // a slot is below both
+    uint32_t *rec;                 // the key set's records
+    const uint8_t *sbox;
+    uint8_t *sg_seeds, *sg_publics;    // the signers' rows, or null: sg_stride 0 leaves the one shared row alone
+    uint64_t sg_stride;
+    uint8_t *sg_peer, *sg_flags;
+    int32_t *status, *accepted;
+    uint8_t *link_id;              // n x 16 B
+    int32_t *mtu;
+    uint8_t *proofs;               // 118 bytes at proofs + i*proof_stride where proof_len[i] is 118
+    uint64_t proof_stride;
+    uint32_t *proof_len;
+    uint32_t *work;
+    uint32_t n;
+};
+uint64_t linkreq_workspace_bytes(uint32_t n, uint32_t m);
+hipError_t launch_link_accept(const LinkReqArgs &a, hipStream_t s);
+// out[i] = rows[i] where mask[i] (null: every item) and rows[i] < n_keys, else 0xFFFFFFFF
+hipError_t launch_rows_select(const uint32_t *rows, const uint8_t *mask, uint32_t n_keys, uint32_t *out, uint32_t n,
+                              hipStream_t s);
+
 // Packet hash list and packet filter (filter_kernels.hip; the layout is
 // described there).  Two generations of slot words and 32-byte hashes; which
 // of them is the current one is a word in device memory that every kernel reads.
@@ -432,5 +472,12 @@ hipError_t launch_key_setup(const uint8_t *keys, uint32_t key_len, uint32_t n_ke
 // outside the fused kernel's (the caller then runs launch_hkdf +
 // launch_key_setup through a temporary).
 hipError_t launch_hkdf_key_setup(const HkdfArgs &a, const uint8_t *sbox, uint32_t *rec, int n_cu, hipStream_t s);
+// The same into chosen records of an existing table of 64-byte keys: item i
+// writes record rows[i], or nothing where rows[i] is 0xFFFFFFFF; rows of one
+// launch are distinct.  count (device, may be null): only the first
+// min(*count, a.n) items exist.  One salt row per item, the fused kernel's
+// shape only (hipErrorNotSupported otherwise).
+hipError_t launch_hkdf_key_setup_rows(const HkdfArgs &a, const uint8_t *sbox, uint32_t *rec, const uint32_t *rows,
+                                      const uint32_t *count, hipStream_t s);
 
 }  // namespace rnstok

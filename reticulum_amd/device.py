@@ -964,6 +964,114 @@ def proof_settle(pkt, pkt_off, fields, link, signers, receipts, proof_status, re
                                                  _p(receipt), n, _stream(stream, pkt.device)))
 
 
+# Link requests (linkreq_kernels.hip): ``destinations`` is a
+# reticulum_amd.link.LinkDestinations, ``links`` a LinkTable, ``signers`` a
+# reticulum_amd.proof.LinkSigners or None.
+
+LINKREQ_ACCEPTED, LINKREQ_NOT_REQUEST, LINKREQ_OTHER_TRANSPORT = 0, 1, 2      # RT_LINKREQ_* (include/rnstok.h)
+LINKREQ_NO_DESTINATION, LINKREQ_NOT_ACCEPTING, LINKREQ_BAD_SIZE, LINKREQ_BAD_MODE = 3, 4, 6, 7
+LINKREQ_DUPLICATE, LINKREQ_NO_SLOT = 8, 9
+DEST_ACCEPTS = 4             # RT_DEST_ACCEPTS, beside LINK_PROVE_ALL and LINK_HAS_CHANNEL
+LRPROOF_LEN = 118            # flags, hops, link id (16), context, signature (64), pub (32), signalling (3)
+
+
+def link_accept(ks: KeySet, links, destinations, transport_identity, pkt, pkt_off, fields, slots, ephemeral_privates,
+                status, accepted, link_id, link_mtu, lr_proofs, lr_proof_len, nh_mtu=500, signers=None, stream=None):
+    """The responder side of link establishment (Transport.py:2127-2158,
+    Destination.py:414-435, Link.py:186-227, 336-376) over packet_unpack's
+    records, each request read inside its packet pkt[pkt_off[i]:].  ``slots``
+    ((m,) int32) is the caller's free list and ``ephemeral_privates`` ((m, 32)
+    uint8) its randomness: valid request r in index order takes slots[r] and
+    row r.  ``nh_mtu`` is the receiving interface's next-hop MTU
+    (Transport.py:2138-2141), None for an interface without HW_MTU.
+
+    status[i] ((n,) int32) is LINKREQ_ACCEPTED, NOT_REQUEST, OTHER_TRANSPORT,
+    NO_DESTINATION, NOT_ACCEPTING, BAD_SIZE, BAD_MODE, DUPLICATE (the id is in
+    ``links`` or at a lower index of the batch) or NO_SLOT; accepted[i] ((n,)
+    int32) the slot or -1; link_id ((n, 16) uint8) and link_mtu ((n,) int32)
+    are set for every valid request; row i of lr_proofs ((n, >=118) uint8 at
+    any row stride) is the LRPROOF packet where lr_proof_len[i] ((n,) int32) is
+    118, untouched where it is 0.  When the call has run, ``links`` maps each
+    accepted id to its slot, record slot of ``ks`` (64-byte keys) is the
+    link's handshake key, and with ``signers`` the slot's rows hold the peer's
+    signing key, the destination's flags and (one row per link) its seed and
+    public key.  Nothing is synchronised, and neither shared secrets nor
+    derived keys leave the device."""
+    n = _check_fields(fields)
+    _check_u8(pkt, transport_identity, ephemeral_privates, link_id, lr_proofs)
+    if ks.key_len != 64:
+        raise ValueError("a link's key set holds 64-byte keys")
+    if pkt.dim() != 1 or not pkt.is_cuda or not pkt.is_contiguous():
+        raise ValueError("pkt must be a flat contiguous uint8 buffer in device memory")
+    _check_i64(n, pkt_off=pkt_off)
+    _check_i32(n, status=status, accepted=accepted, link_mtu=link_mtu, lr_proof_len=lr_proof_len)
+    if any(t is None for t in (pkt_off, status, accepted, link_mtu, lr_proof_len)):
+        raise ValueError("pkt_off, status, accepted, link_mtu and lr_proof_len are required")
+    if transport_identity.numel() != 16 or not transport_identity.is_contiguous():
+        raise ValueError("transport_identity is the node's 16-byte transport id")
+    m = slots.numel()
+    _check_i32(m, slots=slots)
+    if ephemeral_privates.dim() != 2 or ephemeral_privates.shape != (m, 32) or not ephemeral_privates.is_contiguous():
+        raise ValueError(f"ephemeral_privates must be a contiguous ({m}, 32) uint8 tensor, one row per slot")
+    if link_id.dim() != 2 or link_id.shape != (n, 16) or not link_id.is_contiguous():
+        raise ValueError(f"link_id must be a contiguous ({n}, 16) uint8 tensor")
+    _check_rows("lr_proofs", lr_proofs, n, LRPROOF_LEN)
+    d = destinations
+    sg = [None, None, 0, None, None]
+    n_links = 0xFFFFFFFF
+    if signers is not None:
+        n_links = int(signers.n_links)
+        sd, stride = _ed_rows("signers.seeds", signers.seeds, n_links, 32)
+        pk, pk_stride = _ed_rows("signers.publics", signers.publics, n_links, 32)
+        if pk_stride != stride:
+            raise ValueError("signers.seeds and signers.publics must have the same rows")
+        if stride == 0 and d.n > 1:
+            raise ValueError("signers with one shared seed row serve one destination; give them one row per link")
+        pp = signers.peer_publics
+        if pp.dim() != 2 or pp.shape != (n_links, 32) or not pp.is_contiguous():
+            raise ValueError(f"signers.peer_publics must be a contiguous ({n_links}, 32) uint8 tensor")
+        if signers.flags.numel() != n_links or not signers.flags.is_contiguous():
+            raise ValueError(f"signers.flags must be a contiguous ({n_links},) uint8 tensor")
+        sg = [sd, pk, stride, _p(pp), _p(signers.flags)]
+        _same_device(pkt.device, signers.seeds, signers.publics, pp, signers.flags)
+    _same_device(pkt.device, pkt_off, fields, transport_identity, slots, ephemeral_privates, status, accepted, link_id,
+                 link_mtu, lr_proofs, lr_proof_len, d.seeds, d.publics, d.flags)
+    if n == 0:
+        return
+    nh = -1 if nh_mtu is None else int(nh_mtu)
+    if not -1 <= nh <= 0xFFFFFFFF:
+        raise ValueError("nh_mtu must be a uint32 or None")
+    _native.check(_native.load().rt_link_accept(
+        links.handle, ks.handle, d.table.handle, _p(d.seeds), _p(d.publics), _p(d.flags), d.n, _p(transport_identity),
+        nh, _p(pkt), _p(pkt_off), _p(fields), n, _p(slots) if m else None, _p(ephemeral_privates) if m else None, m,
+        n_links, sg[0], sg[1], sg[2], sg[3], sg[4], _p(status), _p(accepted), _p(link_id), _p(link_mtu),
+        _p_rows(lr_proofs), max(lr_proofs.stride(0), LRPROOF_LEN), _p(lr_proof_len), _stream(stream, pkt.device)))
+
+
+def keyset_set_rows_x25519(ks: KeySet, scalars, points, salt, rows, mask=None, point_off=None, stream=None):
+    """Rewrites records of an existing key set of 64-byte keys on the device:
+    for every item i that ``mask`` ((n,) uint8, None: all) selects, record
+    rows[i] ((n,) int32, distinct) becomes Token(hkdf(64, X25519(scalars[i],
+    points[i]), salt[i])); scalars, points and point_off as :func:`x25519`,
+    salt (n, S) with S a multiple of 4 up to 64.  Enqueued on ``stream``:
+    launches on that stream after it see the new rows; ordering other streams
+    is the caller's part."""
+    n = rows.numel()
+    _check_i32(n, rows=rows)
+    _check_u8(salt, mask)
+    if ks.key_len != 64:
+        raise ValueError("rows are rewritten in a key set of 64-byte keys")
+    if salt.dim() != 2 or salt.shape[0] != n or not salt.is_contiguous():
+        raise ValueError(f"salt must be a contiguous ({n}, S) uint8 matrix")
+    if mask is not None and (mask.numel() != n or not mask.is_contiguous()):
+        raise ValueError(f"mask must be a contiguous ({n},) uint8 tensor")
+    sc, sc_stride, pt, pt_stride, off = _x25519_args(scalars, points, point_off, n)
+    _order_after_current(stream, scalars, points, point_off, salt, rows, mask)
+    _native.check(_native.load().rt_keyset_set_rows_x25519(ks.handle, sc, sc_stride, pt, pt_stride, off, _p(salt),
+                                                           salt.stride(0), salt.shape[1], _p(rows), _p(mask), n,
+                                                           _stream(stream, rows.device)))
+
+
 def ifac_mask(pkt, pkt_off, pkt_len, ifac, ifac_key, out, out_off, stream=None):
     """Transport.transmit's IFAC step (Transport.py:1069-1101): packet i plus
     its access code ifac[i] (n, ifac_size) -> pkt_len[i] + ifac_size masked

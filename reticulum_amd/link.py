@@ -10,9 +10,13 @@ in a :class:`KeySet`), ``pipeline.inbound(..., links=table)`` runs the lookup
 and the decision between unpack and decrypt, and :func:`derive_link_keys`
 builds the keys of a batch of links from their handshakes (Link.py:348-361).
 
-Keeping ``KeySet`` and ``LinkTable`` in step is the caller's part: value v of
-the table means key v of the key set the batch is decrypted with
-(INTEGRATION.md §6).
+Value v of the table means key v of the key set the batch is decrypted with
+(INTEGRATION.md §6).  For links that others open to this node the device keeps
+the two in step itself: :class:`LinkDestinations` holds the node's own
+destinations, and ``pipeline.inbound(..., accept=...)`` / ``device.link_accept``
+answer the link requests of a read (Transport.py:2127-2158, Link.py:186-227),
+entering each new link into the table, its key into the key set and its rows
+into the signers under one slot of the caller's free list.
 """
 import contextlib
 import hashlib
@@ -26,6 +30,14 @@ MODE_AES128_CBC, MODE_AES256_CBC = 0x00, 0x01          # Link.py:94-95
 ECPUBSIZE = 64                                        # Link.py:73: X25519 + Ed25519 public keys
 LINK_ID_LEN = 16                                      # Reticulum.TRUNCATED_HASHLENGTH // 8
 HEADER_2 = 0x01
+MTU = 500                                             # Reticulum.MTU: a link's MTU without signalling
+LRPROOF_LEN = 118                                     # Packet.py:170-185 around Link.prove's proof data
+# what became of a record in the link request stage: RT_LINKREQ_* (include/rnstok.h)
+LINKREQ_ACCEPTED, LINKREQ_NOT_REQUEST, LINKREQ_OTHER_TRANSPORT = 0, 1, 2
+LINKREQ_NO_DESTINATION, LINKREQ_NOT_ACCEPTING, LINKREQ_BAD_SIZE, LINKREQ_BAD_MODE = 3, 4, 6, 7
+LINKREQ_DUPLICATE, LINKREQ_NO_SLOT = 8, 9
+# a destination's flags: the two a new link's signer row inherits (proof.PROVE_ALL, proof.HAS_CHANNEL), and
+ACCEPTS, PROVE_ALL, HAS_CHANNEL = 4, 1, 2             # RT_DEST_ACCEPTS, RT_LINK_PROVE_ALL, RT_LINK_HAS_CHANNEL
 
 
 def link_id_from_lr_packet(raw):
@@ -201,3 +213,90 @@ def derive_link_keys(privates, peer_publics, link_ids, mode=MODE_AES256_CBC, dev
     if n < 1 or pub.shape[0] != n or ids.shape[0] != n:
         raise ValueError("privates, peer_publics and link_ids must hold one row per link (at least one)")
     return _dev.derive_keyset_x25519(prv, pub, salt=ids, context=None, key_len=key_len, n=n)
+
+
+class LinkDestinations:
+    """The node's own SINGLE destinations on the device, for the link request
+    stage: a :class:`LinkTable` from 16-byte destination hash to row, and per
+    row the identity's Ed25519 signing seed, its public key (derived once,
+    device.ed25519_public) and a flags byte: ACCEPTS (accept_link_requests,
+    Destination.py:432) and PROVE_ALL | HAS_CHANNEL, which become the flags of
+    a new link's :class:`reticulum_amd.proof.LinkSigners` row (a destination
+    that proves by callback, PROVE_APP, gets neither).
+
+    ``hashes`` (n, 16), ``seeds`` (n, 32) and ``flags`` (n,) may be device
+    tensors, numpy arrays or sequences (of byte strings; flags: of ints).
+    Nothing of it leaves the device."""
+
+    def __init__(self, hashes, seeds, flags, device=None):
+        dev = _torch_device(device)
+        self.device = dev
+        self.hashes = _rows(hashes, LINK_ID_LEN, dev, "destination hashes")
+        self.n = int(self.hashes.shape[0])
+        if self.n < 1:
+            raise ValueError("at least one destination")
+        self.seeds = _rows(seeds, 32, dev, "seeds")
+        if self.seeds.shape[0] != self.n:
+            raise ValueError("seeds must hold one row per destination")
+        if isinstance(flags, torch.Tensor):
+            fl = flags
+        else:
+            fl = np.asarray(flags)
+            if fl.size and (fl.min() < 0 or fl.max() > ACCEPTS | PROVE_ALL | HAS_CHANNEL):
+                raise ValueError("flags are ACCEPTS | PROVE_ALL | HAS_CHANNEL")
+            fl = torch.from_numpy(np.ascontiguousarray(fl, dtype=np.uint8))
+        if fl.dtype != torch.uint8 or fl.numel() != self.n:
+            raise ValueError(f"flags must be ({self.n},) uint8")
+        self.flags = fl.to(dev).contiguous().view(self.n)
+        self.publics = torch.empty_like(self.seeds)
+        _dev.ed25519_public(self.seeds, self.publics)
+        self.table = LinkTable(self.n, device=dev)
+        status = self.table.insert(self.hashes, torch.arange(self.n, dtype=torch.int32, device=dev))
+        if bool((status != 0).any()):                   # once, at construction: reads the status back
+            raise ValueError("destination hashes must be distinct: a repeated one could never reach its row")
+
+
+def accept_requests_batch(raws, ks, links, destinations, transport_identity, slots, ephemeral_privates, nh_mtu=MTU,
+                          signers=None):
+    """The link request stage for callers without torch tensors: ``raws`` is a
+    sequence of raw packets (byte strings, as the interface handed them on),
+    ``transport_identity`` 16 bytes, ``slots`` a sequence of free slots and
+    ``ephemeral_privates`` as many 32-byte strings of fresh randomness
+    (os.urandom, as X25519PrivateKey.generate draws it).  Unpacks the packets
+    and runs device.link_accept over them against ``ks``, ``links``
+    (:class:`LinkTable`), ``destinations`` (:class:`LinkDestinations`) and
+    optional ``signers``.  Returns one dict per packet: ``status`` (LINKREQ_*),
+    ``slot`` (or -1), ``link_id`` and ``mtu`` (for a valid request, else None)
+    and ``lrproof`` (the 118-byte packet to send, or None)."""
+    dev = links.device
+    raws = [bytes(r) for r in raws]
+    n = len(raws)
+    if n == 0:
+        return []
+    off = np.zeros(n, dtype=np.int64)
+    off[1:] = np.cumsum([len(r) for r in raws])[:-1]
+    pkt = torch.from_numpy(np.frombuffer(b"".join(raws) + b"\0", dtype=np.uint8).copy()).to(dev)
+    pkt_off = torch.from_numpy(off).to(dev)
+    pkt_len = torch.tensor([len(r) for r in raws], dtype=torch.int32, device=dev)
+    fields = torch.empty((n, 96), dtype=torch.uint8, device=dev)
+    _dev.packet_unpack(pkt, pkt_off, pkt_len, fields)
+    slots = torch.as_tensor(np.asarray(list(slots), dtype=np.int32)).to(dev)
+    m = slots.numel()
+    eph = _rows(ephemeral_privates, 32, dev, "ephemeral_privates") if m else \
+        torch.empty((0, 32), dtype=torch.uint8, device=dev)
+    tid = torch.from_numpy(np.frombuffer(bytes(transport_identity), dtype=np.uint8).copy()).to(dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    accepted = torch.empty(n, dtype=torch.int32, device=dev)
+    mtu = torch.empty(n, dtype=torch.int32, device=dev)
+    plen = torch.empty(n, dtype=torch.int32, device=dev)
+    ids = torch.empty((n, LINK_ID_LEN), dtype=torch.uint8, device=dev)
+    proofs = torch.zeros((n, 128), dtype=torch.uint8, device=dev)
+    _dev.link_accept(ks, links, destinations, tid, pkt, pkt_off, fields, slots, eph, status, accepted, ids, mtu,
+                     proofs, plen, nh_mtu=nh_mtu, signers=signers)
+    status, accepted, mtu, plen = (t.cpu().numpy() for t in (status, accepted, mtu, plen))
+    ids, proofs = ids.cpu().numpy(), proofs.cpu().numpy()
+    valid = (LINKREQ_ACCEPTED, LINKREQ_DUPLICATE, LINKREQ_NO_SLOT)
+    return [{"status": int(status[i]), "slot": int(accepted[i]),
+             "link_id": ids[i].tobytes() if status[i] in valid else None,
+             "mtu": int(mtu[i]) if status[i] in valid else None,
+             "lrproof": proofs[i, :LRPROOF_LEN].tobytes() if plen[i] == LRPROOF_LEN else None} for i in range(n)]

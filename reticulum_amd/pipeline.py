@@ -22,6 +22,8 @@ Inbound, as the interface's read loop hands frames to Transport:
                              receipts, after the link dispatch)
     Token.decrypt            Token.py:100-114 (Link/Identity.decrypt)
     packets proved           Link.py:943-955, 1140-1145, 378-389 (with signers)
+    link requests answered   Transport.py:2127-2158, Link.py:186-227, 336-376
+                             (with accept, between the filter and the dispatch)
 
 Every stage is one of reticulum_amd.device's kernels, the rearranging of
 offsets and lengths between them included (frames_compact, token_spans), and
@@ -132,7 +134,7 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
 
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
             check_ifac=False, links=None, seen=None, transport_identity=None, transit=None, announces=False,
-            signers=None, receipts=None):
+            signers=None, receipts=None, accept=None):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -236,7 +238,42 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     The proof rows are raw packets: compacting them by ``proof_len`` and
     sending them (ifac_sign, ifac_mask, hdlc_frame) is the caller's part, and
     so are links that prove by callback (PROVE_APP: flags 0, the caller signs
-    the ``packet_hash`` column of ``fields`` with device.ed25519_sign)."""
+    the ``packet_hash`` column of ``fields`` with device.ed25519_sign).
+
+    ``accept`` answers the link requests of the read that are addressed to the
+    node's own destinations (device.link_accept, after unpack and the packet
+    filter and before the link dispatch; Transport.py:2127-2158,
+    Destination.py:414-435, Link.py:186-227, 336-376).  It is a dict, or an
+    object with these attributes: ``destinations`` (a
+    :class:`reticulum_amd.link.LinkDestinations`), ``slots`` ((m,) int32, the
+    caller's free slots), ``ephemeral_privates`` ((m, 32) uint8, fresh
+    randomness, row r for the r-th valid request of the read) and ``nh_mtu``
+    (the interface's next-hop MTU, Transport.py:2138-2141; None for an
+    interface without HW_MTU; default 500).  It needs ``links``,
+    ``transport_identity`` and a ``ks`` of 64-byte keys.  An accepted request
+    enters ``links``, record slot of ``ks`` and, with ``signers``, the slot's
+    rows before the dispatch runs, so a packet on the new link that follows
+    its request in the same read is decrypted under the new key (and proved,
+    for a PROVE_ALL destination) as the reference's loop over the frames would.
+    One difference: a link packet that precedes its request in the same read
+    is dispatched too, where the reference finds no link yet.  A request an
+    earlier stage dropped (a forged access code, a replay) has ok = 0 and reads
+    LINKREQ_NOT_REQUEST.  The result gains ``linkreq_status`` (int32 per
+    frame, device.LINKREQ_*), ``accepted_link`` (int32: the slot or -1),
+    ``link_id`` (uint8, max_pairs x 16) and ``link_mtu`` (int32) for every valid
+    request, ``lr_proofs`` (uint8, max_pairs x 128: the 118-byte LRPROOF packet
+    where ``lr_proof_len`` is 118) and ``lr_proof_len``.  Sending the rows and
+    the links' host state (watchdog, timeouts, callbacks, the LRRTT that
+    activates the link) stay with the caller, keyed by the slot.  Out of scope:
+    the initiator side, requests in transit for other nodes, PROVE_APP and the
+    per-interface ingress limits."""
+    if accept is not None:
+        get = accept.get if isinstance(accept, dict) else lambda k, d=None: getattr(accept, k, d)
+        if links is None or transport_identity is None or ks.key_len != 64:
+            raise ValueError("accept needs links, transport_identity and a key set of 64-byte keys")
+        acc = (get("destinations"), get("slots"), get("ephemeral_privates"), get("nh_mtu", 500))
+        if acc[0] is None or acc[1] is None or acc[2] is None:
+            raise ValueError("accept bundles destinations, slots, ephemeral_privates and nh_mtu")
     if seen is not None and transport_identity is None:
         raise ValueError("seen needs transport_identity, the node's 16-byte transport id")
     if (signers is not None or receipts is not None) and links is None:
@@ -299,6 +336,16 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
             announce_status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
             announce_identity = torch.empty((max_pairs, 16), dtype=torch.uint8, device=dev)
             device.announce_validate(un, f_off, fields, announce_status, announce_identity, stream=stream)
+        if accept is not None:
+            linkreq_status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            accepted_link = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            link_id = torch.empty((max_pairs, 16), dtype=torch.uint8, device=dev)
+            link_mtu = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            lr_proofs = torch.empty((max_pairs, device.LINE), dtype=torch.uint8, device=dev)
+            lr_proof_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            device.link_accept(ks, links, acc[0], transport_identity, un, f_off, fields, acc[1], acc[2],
+                               linkreq_status, accepted_link, link_id, link_mtu, lr_proofs, lr_proof_len,
+                               nh_mtu=acc[3], signers=signers, stream=stream)
         tok_off = torch.empty(max_pairs, dtype=torch.int64, device=dev)
         tok_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
         key_idx = None
@@ -337,6 +384,9 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
         res.update(proofs=proofs, proof_len=proof_len)
     if receipts is not None:
         res.update(proof_status=proof_status, receipt=receipt)
+    if accept is not None:
+        res.update(linkreq_status=linkreq_status, accepted_link=accepted_link, link_id=link_id, link_mtu=link_mtu,
+                   lr_proofs=lr_proofs, lr_proof_len=lr_proof_len)
     return res
 
 
