@@ -43,6 +43,8 @@
  *   rt_link_accept     link requests answered      RNS/Transport.py:2127-2158, RNS/Destination.py:414-435,
  *                      (responder side)            RNS/Link.py:186-227, 336-376, RNS/Packet.py:170-185
  *   rt_keyset_set_rows_x25519  Link.handshake's key into a record of an existing key set  RNS/Link.py:348-361
+ *   rt_link_establish  link request proofs        RNS/Transport.py:2270-2318, RNS/Link.py:391-451, 326-333,
+ *                      validated (initiator side)  348-361
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
@@ -915,6 +917,101 @@ int rt_keyset_set_rows_x25519(rt_keyset *ks, const uint8_t *scalars, uint64_t sc
                               uint64_t point_stride, const uint64_t *point_off, const uint8_t *salt,
                               uint64_t salt_stride, uint32_t salt_len, const uint32_t *rows, const uint8_t *mask,
                               uint32_t n, void *stream);
+
+/* ---- link request proofs (Transport.py:2270-2318, Link.py:391-451, 326-333, 348-361) */
+/* The initiator side of link establishment: the LRPROOF packets of a read that
+ * answer the node's own link requests, over the n records rt_packet_unpack
+ * wrote (after rt_packet_filter where there is one, which defers the proofs'
+ * hashes to this stage) and before rt_link_spans, so that the read's own
+ * packets on a link that comes up find it.
+ *
+ * The pending links are an rt_linktable from 16-byte link id to a row
+ * 0 .. n_rows-1 of per-row arrays in device memory: row_privates (32 B: the
+ * link's ephemeral X25519 private key), row_dest_publics (32 B: the
+ * destination identity's Ed25519 public key), row_sig_seeds / row_sig_publics
+ * (32 B each: the link's own Ed25519 seed and rt_ed25519_public of it),
+ * row_flags (one byte, RT_LINK_PROVE_ALL | RT_LINK_HAS_CHANNEL: the new link's
+ * signer flags), row_slots (int32: the slot the link takes in `links`, `ks`
+ * and the signers; distinct among the pending links, as a free list gives
+ * them: rows that share a slot would write one key record), and the link's state, which the call changes: row_hops
+ * (int32: Link.expected_hops, compared with the received hop count + 1 as
+ * Transport.inbound counts it), row_rebalanced (one byte), row_state (one byte,
+ * RT_PENDING_*: Link.PENDING, HANDSHAKE, ACTIVE, CLOSED) and row_mtu (int32).
+ * The records are taken as if the packets came one after another in index
+ * order.  status[i], the first rule that applies:
+ *   RT_LRPROOF_NOT_LRPROOF    fields[i].ok == 0, not a PROOF, or context not
+ *                             LRPROOF (0xFF); the destination type is not
+ *                             read, as the reference does not read it;
+ *   RT_LRPROOF_NO_LINK        the destination hash is not in `pending`;
+ *   RT_LRPROOF_NOT_PENDING    the row's state is not PENDING, or a record at a
+ *                             lower index of the batch decided the link;
+ *   with hops + 1 == row_hops:
+ *   RT_LRPROOF_BAD_MODE       data longer than 96 bytes whose mode bits
+ *                             (data[96] >> 5) are not AES-256-CBC: the link is
+ *                             CLOSED;
+ *   RT_LRPROOF_BAD_SIZE       data of neither 96 nor 99 bytes: ignored, the
+ *                             link stays PENDING;
+ *   RT_LRPROOF_BAD_SIGNATURE  data[:64] is no signature of  link id ‖
+ *                             data[64:96] ‖ row_dest_publics ‖ signalling  under
+ *                             row_dest_publics, where signalling is nothing (96
+ *                             bytes) or Link.signalling_bytes of the 21-bit MTU
+ *                             in data[96:99], encoded anew: the link stays in
+ *                             HANDSHAKE for good (the reference has derived
+ *                             its key by then; the device settles the
+ *                             signature first and runs no ladder for it);
+ *   RT_LRPROOF_NO_SLOT        the signature holds and row_slots is not below
+ *                             rt_keyset_size and n_links, or `links` has no
+ *                             room or holds the id: the row stays PENDING;
+ *   RT_LRPROOF_ACTIVATED      the link is ACTIVE when the call has run;
+ *   with another hop count:
+ *   RT_LRPROOF_ACTIVATED      96 or 99 bytes, the right mode, a row that was
+ *                             not rebalanced before and a signature that
+ *                             holds: row_rebalanced = 1, row_hops = hops + 1,
+ *                             then as above (NO_SLOT leaves the row untouched);
+ *   RT_LRPROOF_HOPS           anything else: ignored, the link stays PENDING.
+ * The lowest index that decides a link (BAD_MODE, BAD_SIGNATURE, NO_SLOT,
+ * ACTIVATED) does so whatever the scheduling.  established[i] is the slot of an
+ * activated link (-1 elsewhere) and mtu[i] its MTU (the confirmed MTU, or 500;
+ * 0 elsewhere), which is also row_mtu.  For an activated link, with l its slot:
+ *   - `links` maps the link id to l (rt_linktable_insert's semantics);
+ *   - record l of `ks` (64-byte keys) is Token(hkdf(64, X25519(row_privates,
+ *     data[64:96]), salt = link id)), Link.handshake's key (data[64:96] as a
+ *     256-bit value mod p, bit 255 not masked; constant time in the private key);
+ *   - with sg_peer_publics given (n_links x 32) the signers' rows of l are
+ *     filled: sg_peer_publics[l] = row_dest_publics, sg_flags[l] = row_flags & 3
+ *     and, where sg_stride is not 0, sg_seeds / sg_publics at l*sg_stride = the
+ *     row's seed and public key.
+ * With `seen` (or NULL) the packet hashes of the records that reached
+ * validate_proof are entered into the hash list as rt_hashlist_add does
+ * (Transport.py:2314): those whose hop count matched, after the rebalance where
+ * one fired, on a link still among the pending ones (not ACTIVE before the
+ * record), NO_SLOT excepted so that a proof sent again can bring the link up.
+ * The pending table itself is not changed: removing a row (the caller's
+ * watchdog, or after reading an ACTIVE state back) is rt_linktable_remove.
+ * Nothing private leaves the device.  DEVICE pointers; the call only enqueues
+ * on the stream and takes its place in the host order of `pending`, `links` and
+ * `seen`; key records are written in stream order.  n == 0 is RT_OK. */
+#define RT_PENDING_PENDING   0
+#define RT_PENDING_HANDSHAKE 1
+#define RT_PENDING_ACTIVE    2
+#define RT_PENDING_CLOSED    4
+#define RT_LRPROOF_ACTIVATED     0
+#define RT_LRPROOF_NOT_LRPROOF   1
+#define RT_LRPROOF_NO_LINK       2
+#define RT_LRPROOF_NOT_PENDING   3
+#define RT_LRPROOF_HOPS          4
+#define RT_LRPROOF_BAD_SIZE      6
+#define RT_LRPROOF_BAD_MODE      7
+#define RT_LRPROOF_BAD_SIGNATURE 8
+#define RT_LRPROOF_NO_SLOT       9
+int rt_link_establish(rt_linktable *pending, uint32_t n_rows, const uint8_t *row_privates,
+                      const uint8_t *row_dest_publics, const uint8_t *row_sig_seeds, const uint8_t *row_sig_publics,
+                      const uint8_t *row_flags, const int32_t *row_slots, int32_t *row_hops, uint8_t *row_rebalanced,
+                      uint8_t *row_state, int32_t *row_mtu, rt_linktable *links, rt_keyset *ks, uint32_t n_links,
+                      const uint8_t *pkt, const uint64_t *pkt_off, const rt_packet_fields *fields, uint32_t n,
+                      uint8_t *sg_seeds, uint8_t *sg_publics, uint64_t sg_stride, uint8_t *sg_peer_publics,
+                      uint8_t *sg_flags, rt_hashlist *seen, int32_t *status, int32_t *established, int32_t *mtu,
+                      void *stream);
 
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from

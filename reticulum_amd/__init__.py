@@ -62,6 +62,7 @@ from .resource import prepare_resource, resource_hashes, validate_proof, verify_
 from . import wire  # noqa: F401
 from . import link  # noqa: F401
 from .link import LinkDestinations, LinkTable, accept_requests_batch, derive_link_keys, link_id_from_lr_packet  # noqa: F401
+from .link import PendingLinks, establish_batch, open_requests_batch, pack_rtt  # noqa: F401
 from . import filter  # noqa: F401
 from .filter import PacketHashlist  # noqa: F401
 from . import proof  # noqa: F401

@@ -5,14 +5,6 @@
 // table's (link_host.h), and so is the ordering of the calls (capi_table.h).
 #include "capi_table.h"
 
-struct rt_hashlist {
-    rt_ctx *ctx = nullptr;
-    HashList l{};
-    std::mutex mu;
-    hipStream_t last = nullptr;
-    hipEvent_t done = nullptr;
-};
-
 namespace {
 
 int check_list(const rt_hashlist *list) {

@@ -20,6 +20,16 @@ struct rt_linktable {
     uint32_t ticket = 0;           // of the latest rebuild enqueued
 };
 
+// The packet hash list (capi_filter.hip; the link request proofs enter hashes
+// into it, capi_lrproof.hip), ordered as a table is.
+struct rt_hashlist {
+    rt_ctx *ctx = nullptr;
+    HashList l{};
+    std::mutex mu;
+    hipStream_t last = nullptr;
+    hipEvent_t done = nullptr;
+};
+
 // Before an insert of n items, with the table's lock held: enqueues the rebuild
 // that reclaims removed slots when the table's book asks for one (capi_link.hip).
 hipError_t link_reclaim(rt_linktable *tab, uint32_t n, hipStream_t s);

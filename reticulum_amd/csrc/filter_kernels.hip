@@ -65,6 +65,10 @@ template <bool FILTER>
 __global__ __launch_bounds__(TABLE_THREADS) void k_filter_claim(FilterArgs a, const uint8_t *base) {
     const uint32_t i = blockIdx.x * TABLE_THREADS + threadIdx.x;
     if (i >= a.n) return;
+    if (!FILTER && a.mask && !a.mask[i]) {       // a masked add: the item is left out
+        a.status[i] = RT_FILTER_PASS;
+        return;
+    }
     bool consult = false, remember = true, dup_passes = false;
     int32_t dup_status = RT_FILTER_DUPLICATE;
     if (FILTER) {
@@ -230,9 +234,10 @@ hipError_t launch_packet_filter(const FilterArgs &a, hipStream_t s) {
     return launch_enter<true>(a, nullptr, s);
 }
 
-hipError_t launch_hashlist_add(const HashList &l, const uint8_t *hashes, int32_t *scratch, uint32_t n, hipStream_t s) {
+hipError_t launch_hashlist_add(const HashList &l, const uint8_t *hashes, int32_t *scratch, uint32_t n, hipStream_t s,
+                               const uint8_t *mask) {
     if (n == 0) return hipSuccess;
-    return launch_enter<false>(FilterArgs{l, LinkTab{}, nullptr, nullptr, scratch, n}, hashes, s);
+    return launch_enter<false>(FilterArgs{l, LinkTab{}, nullptr, nullptr, scratch, n, mask}, hashes, s);
 }
 
 // Remove, as the link table's, from the current generation.

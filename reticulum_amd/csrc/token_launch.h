@@ -378,6 +378,40 @@ hipError_t launch_link_accept(const LinkReqArgs &a, hipStream_t s);
 hipError_t launch_rows_select(const uint32_t *rows, const uint8_t *mask, uint32_t n_keys, uint32_t *out, uint32_t n,
                               hipStream_t s);
 
+// Link request proofs (lrproof_kernels.hip): the records rt_packet_unpack
+// wrote, the pending links (a link table from link id to row, beside the rows'
+// keys and state), and the link table, key records and signers' rows the
+// activated links go into.  `work` is lrproof_workspace_bytes(n, n_rows) of
+// device memory the launch may use until it has run; `remember` (n bytes, or
+// null) and `hashes` (n x 32 B) receive which records' packet hashes the hash
+// list is to learn, and the hashes of those.
+struct LrProofArgs {
+    const uint8_t *pkt;
+    const uint64_t *pkt_off;
+    const uint8_t *fields;         // n rt_packet_fields records
+    LinkTab pending;               // link id -> row
+    uint32_t n_rows;
+    const uint8_t *row_privates, *row_dest_publics, *row_sig_seeds, *row_sig_publics;   // n_rows x 32 B each
+    const uint8_t *row_flags;
+    const int32_t *row_slots;
+    int32_t *row_hops;
+    uint8_t *row_rebalanced, *row_state;
+    int32_t *row_mtu;
+    LinkTab links;                 // link id -> slot
+    uint32_t n_keys, n_links;      // a slot is below both
+    uint32_t *rec;                 // the key set's records
+    const uint8_t *sbox;
+    uint8_t *sg_seeds, *sg_publics;
+    uint64_t sg_stride;
+    uint8_t *sg_peer, *sg_flags;
+    int32_t *status, *established, *mtu;
+    uint8_t *remember, *hashes;
+    uint32_t *work;
+    uint32_t n;
+};
+uint64_t lrproof_workspace_bytes(uint32_t n, uint32_t n_rows);
+hipError_t launch_link_establish(const LrProofArgs &a, hipStream_t s);
+
 // Packet hash list and packet filter (filter_kernels.hip; the layout is
 // described there).  Two generations of slot words and 32-byte hashes; which
 // of them is the current one is a word in device memory that every kernel reads.
@@ -402,10 +436,12 @@ struct FilterArgs {
     uint8_t *fields;               // n rt_packet_fields records
     int32_t *status;
     uint32_t n;
+    const uint8_t *mask;           // launch_hashlist_add only: items with mask[i] == 0 are left out; null: none is
 };
 // status doubles as the scratch between each call's kernels
 hipError_t launch_packet_filter(const FilterArgs &a, hipStream_t s);
-hipError_t launch_hashlist_add(const HashList &l, const uint8_t *hashes, int32_t *scratch, uint32_t n, hipStream_t s);
+hipError_t launch_hashlist_add(const HashList &l, const uint8_t *hashes, int32_t *scratch, uint32_t n, hipStream_t s,
+                               const uint8_t *mask = nullptr);
 hipError_t launch_hashlist_remove(const HashList &l, const uint8_t *hashes, int32_t *status, uint32_t n,
                                   hipStream_t s);
 hipError_t launch_hashlist_contains(const HashList &l, const uint8_t *hashes, uint8_t *found_out, uint32_t n,

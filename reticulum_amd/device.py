@@ -1072,6 +1072,79 @@ def keyset_set_rows_x25519(ks: KeySet, scalars, points, salt, rows, mask=None, p
                                                            _stream(stream, rows.device)))
 
 
+# Link request proofs (lrproof_kernels.hip): ``pending`` is a
+# reticulum_amd.link.PendingLinks, ``links`` a LinkTable, ``signers`` a
+# reticulum_amd.proof.LinkSigners or None, ``seen`` a
+# reticulum_amd.filter.PacketHashlist or None.
+
+LRPROOF_ACTIVATED, LRPROOF_NOT_LRPROOF, LRPROOF_NO_LINK, LRPROOF_NOT_PENDING = 0, 1, 2, 3   # RT_LRPROOF_*
+LRPROOF_HOPS, LRPROOF_BAD_SIZE, LRPROOF_BAD_MODE, LRPROOF_BAD_SIGNATURE, LRPROOF_NO_SLOT = 4, 6, 7, 8, 9
+PENDING_PENDING, PENDING_HANDSHAKE, PENDING_ACTIVE, PENDING_CLOSED = 0, 1, 2, 4            # RT_PENDING_*: Link's
+
+
+def link_establish(ks: KeySet, links, pending, pkt, pkt_off, fields, status, established, link_mtu, signers=None,
+                   seen=None, stream=None):
+    """The initiator side of link establishment (Transport.py:2270-2318,
+    Link.py:391-451, 348-361) over packet_unpack's records, each proof read
+    inside its packet pkt[pkt_off[i]:], as if the packets came one after
+    another in index order.  ``pending`` holds the links this node has
+    requested: their ephemeral keys, the destinations' signing keys, the slots
+    they are to take, and their state.
+
+    status[i] ((n,) int32) is LRPROOF_ACTIVATED, NOT_LRPROOF, NO_LINK,
+    NOT_PENDING (the link is not PENDING, or a lower index of the batch decided
+    it), HOPS or BAD_SIZE (ignored: the link stays PENDING), BAD_MODE (the link
+    is CLOSED), BAD_SIGNATURE (the link stays in HANDSHAKE for good) or NO_SLOT
+    (the row's slot is not below ks.n_keys and signers.n_links, or ``links``
+    has no room: the link stays PENDING); established[i] ((n,) int32) the slot
+    or -1 and link_mtu[i] ((n,) int32) the link's MTU or 0.  When the call has
+    run, ``links`` maps each activated link id to its slot, record slot of
+    ``ks`` (64-byte keys) is the link's handshake key, with ``signers`` the
+    slot's rows hold the destination's signing key, the row's flags and (one
+    row per link) the link's own seed and public key, and the rows of
+    ``pending`` carry the new state, hops, rebalanced and mtu.  With ``seen``
+    the hashes of the proofs that reached Link.validate_proof enter the hash
+    list (Transport.py:2314).  Nothing is synchronised, and neither private
+    keys, shared secrets nor derived keys leave the device."""
+    n = _check_fields(fields)
+    _check_u8(pkt)
+    if ks.key_len != 64:
+        raise ValueError("a link's key set holds 64-byte keys")
+    if pkt.dim() != 1 or not pkt.is_cuda or not pkt.is_contiguous():
+        raise ValueError("pkt must be a flat contiguous uint8 buffer in device memory")
+    _check_i64(n, pkt_off=pkt_off)
+    _check_i32(n, status=status, established=established, link_mtu=link_mtu)
+    if any(t is None for t in (pkt_off, status, established, link_mtu)):
+        raise ValueError("pkt_off, status, established and link_mtu are required")
+    p = pending
+    sg = [None, None, 0, None, None]
+    n_links = 0xFFFFFFFF
+    if signers is not None:
+        n_links = int(signers.n_links)
+        sd, stride = _ed_rows("signers.seeds", signers.seeds, n_links, 32)
+        pk, pk_stride = _ed_rows("signers.publics", signers.publics, n_links, 32)
+        if pk_stride != stride:
+            raise ValueError("signers.seeds and signers.publics must have the same rows")
+        if stride == 0:
+            raise ValueError("a link this node opens signs with its own key: give the signers one row per link")
+        pp = signers.peer_publics
+        if pp.dim() != 2 or pp.shape != (n_links, 32) or not pp.is_contiguous():
+            raise ValueError(f"signers.peer_publics must be a contiguous ({n_links}, 32) uint8 tensor")
+        if signers.flags.numel() != n_links or not signers.flags.is_contiguous():
+            raise ValueError(f"signers.flags must be a contiguous ({n_links},) uint8 tensor")
+        sg = [sd, pk, stride, _p(pp), _p(signers.flags)]
+        _same_device(pkt.device, signers.seeds, signers.publics, pp, signers.flags)
+    _same_device(pkt.device, pkt_off, fields, status, established, link_mtu, p.privates, p.row_state)
+    if n == 0:
+        return
+    _native.check(_native.load().rt_link_establish(
+        p.table.handle, p.max_pending, _p(p.privates), _p(p.dest_publics), _p(p.sig_seeds), _p(p.sig_publics),
+        _p(p.flags), _p(p.slots), _p(p.expected_hops), _p(p.rebalanced), _p(p.row_state), _p(p.mtu), links.handle,
+        ks.handle, n_links, _p(pkt), _p(pkt_off), _p(fields), n, sg[0], sg[1], sg[2], sg[3], sg[4],
+        seen.handle if seen is not None else None, _p(status), _p(established), _p(link_mtu),
+        _stream(stream, pkt.device)))
+
+
 def ifac_mask(pkt, pkt_off, pkt_len, ifac, ifac_key, out, out_off, stream=None):
     """Transport.transmit's IFAC step (Transport.py:1069-1101): packet i plus
     its access code ifac[i] (n, ifac_size) -> pkt_len[i] + ifac_size masked

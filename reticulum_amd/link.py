@@ -300,3 +300,256 @@ def accept_requests_batch(raws, ks, links, destinations, transport_identity, slo
              "link_id": ids[i].tobytes() if status[i] in valid else None,
              "mtu": int(mtu[i]) if status[i] in valid else None,
              "lrproof": proofs[i, :LRPROOF_LEN].tobytes() if plen[i] == LRPROOF_LEN else None} for i in range(n)]
+
+
+# Link request proofs: the initiator side (lrproof_kernels.hip).  A link's
+# state is the reference's (Link.PENDING, HANDSHAKE, ACTIVE, CLOSED), and what
+# became of a record RT_LRPROOF_* (include/rnstok.h).
+PENDING, HANDSHAKE, ACTIVE, CLOSED = 0x00, 0x01, 0x02, 0x04
+LRPROOF_ACTIVATED, LRPROOF_NOT_LRPROOF, LRPROOF_NO_LINK, LRPROOF_NOT_PENDING = 0, 1, 2, 3
+LRPROOF_HOPS, LRPROOF_BAD_SIZE, LRPROOF_BAD_MODE, LRPROOF_BAD_SIGNATURE, LRPROOF_NO_SLOT = 4, 6, 7, 8, 9
+CONTEXT_LRRTT = 0xFE                                  # Packet.LRRTT
+MTU_BYTEMASK = 0x1FFFFF                               # Link.MTU_BYTEMASK
+
+
+def signalling_bytes(mtu, mode=MODE_AES256_CBC):
+    """Link.signalling_bytes (Link.py:148-151) for the one enabled mode."""
+    if mode != MODE_AES256_CBC:
+        raise TypeError(f"Requested link mode {mode} not enabled")
+    return ((mtu & MTU_BYTEMASK) + (((mode << 5) & 0xE0) << 16)).to_bytes(3, "big")
+
+
+def pack_rtt(rtt):
+    """The LRRTT packet's plaintext (Link.py:435): umsgpack.packb of a float,
+    0xcb and the big-endian double, 9 bytes.  The caller sends it on the new
+    link with ``outbound(..., key_idx=slot, context=CONTEXT_LRRTT)``; the RTT is
+    host time and the token's IV fresh randomness, both the caller's."""
+    import struct
+    return b"\xcb" + struct.pack(">d", float(rtt))
+
+
+class PendingLinks:
+    """The links this node has requested and that wait for their proof
+    (Transport.pending_links), on the device: a :class:`LinkTable` from the
+    16-byte link id to a row, and per row the initiator's ephemeral X25519
+    private key, the destination identity's Ed25519 public key, the link's own
+    Ed25519 seed (its ``sig_prv``) and public key, the flags of its
+    :class:`reticulum_amd.proof.LinkSigners` row, the slot it is to take in
+    ``links`` / ``ks`` / ``signers``, and its state as the reference keeps it:
+    ``expected_hops``, ``rebalanced``, ``state`` (PENDING, HANDSHAKE, ACTIVE,
+    CLOSED) and ``mtu`` (written on activation).  The slots of the pending
+    links are distinct, as a free list gives them: two rows with one slot
+    would both come up and write the same key record and signer row.
+    ``pipeline.inbound(..., establish=pending)`` / ``device.link_establish``
+    validate the LRPROOFs of a read against it.
+
+    ``add`` and ``remove`` are batched and enqueue on ``stream`` without
+    synchronising; which row an id has is kept on the host, so the ids are host
+    data (bytes, or anything ``bytes()`` takes).  ``state()`` and ``hops()``
+    read back for the caller's bookkeeping (the path table's rebalance,
+    callbacks, the LRRTT).  Nothing private leaves the device."""
+
+    def __init__(self, max_pending, device=None):
+        self.table = LinkTable(max_pending, device=device)
+        dev = self.device = self.table.device
+        n = self.max_pending = self.table.max_links
+        z8 = lambda *shape: torch.zeros(shape, dtype=torch.uint8, device=dev)     # noqa: E731
+        self.privates, self.dest_publics, self.sig_seeds, self.sig_publics = (z8(n, 32) for _ in range(4))
+        self.flags, self.rebalanced = z8(n), z8(n)
+        self.row_state = torch.full((n,), CLOSED, dtype=torch.uint8, device=dev)
+        self.slots = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        self.expected_hops = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.mtu = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._row = {}                                  # link id -> row
+        self._free = list(range(n - 1, -1, -1))
+
+    def __len__(self):
+        return len(self._row)
+
+    def row_of(self, link_id):
+        """The row of a pending link, or None."""
+        return self._row.get(bytes(link_id))
+
+    def add(self, link_ids, privates, dest_sig_publics, sig_seeds, flags, slots, expected_hops, stream=None):
+        """Enter links.  Returns the (n,) int32 numpy status: device.LINK_OK,
+        LINK_DUPLICATE (the id is pending, or comes earlier in this batch: the
+        earlier one stays) or LINK_FULL (no free row)."""
+        ids = [bytes(i) for i in link_ids]
+        n = len(ids)
+        if any(len(i) != LINK_ID_LEN for i in ids):
+            raise ValueError("link ids are 16 bytes each")
+        dev = self.device
+
+        def rows_of(x, width, name):
+            t = _rows(x, width, dev, name)
+            if t.shape[0] != n:
+                raise ValueError(f"{name} must hold one row per link")
+            return t
+
+        def ints(x, dtype, name):
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x), dtype=dtype)
+            if t.numel() != n:
+                raise ValueError(f"{name} must hold one value per link")
+            return t.to(dev, dtype).view(n)
+
+        # every input is checked before a row is taken: a call that raises leaves the links as they were
+        with _on(stream):
+            prv, pub = rows_of(privates, 32, "privates"), rows_of(dest_sig_publics, 32, "dest_sig_publics")
+            seeds = rows_of(sig_seeds, 32, "sig_seeds")
+            fl, sl = ints(flags, torch.uint8, "flags"), ints(slots, torch.int32, "slots")
+            hops = ints(expected_hops, torch.int32, "expected_hops")
+        status = np.zeros(n, dtype=np.int32)
+        rows, take, taken = [], [], set()
+        free = len(self._free)
+        for k, i in enumerate(ids):
+            if i in self._row or i in taken:
+                status[k] = 1
+            elif len(take) == free:
+                status[k] = 2
+            else:
+                taken.add(i)
+                take.append(k)
+        if not take:
+            return status
+        for k in take:
+            self._row[ids[k]] = self._free.pop()
+            rows.append(self._row[ids[k]])
+        with _on(stream):
+            pick = torch.as_tensor(take, dtype=torch.int64).to(dev)
+            r = torch.as_tensor(rows, dtype=torch.int64).to(dev)
+            seeds = seeds[pick].contiguous()
+            publics = torch.empty_like(seeds)
+        _dev.ed25519_public(seeds, publics, stream=stream)
+        with _on(stream):
+            self.privates[r] = prv[pick]
+            self.dest_publics[r] = pub[pick]
+            self.sig_seeds[r] = seeds
+            self.sig_publics[r] = publics
+            self.flags[r] = fl[pick]
+            self.slots[r] = sl[pick]
+            self.expected_hops[r] = hops[pick]
+            self.rebalanced[r] = 0
+            self.mtu[r] = 0
+            self.row_state[r] = PENDING
+        # the table holds max_pending ids and the host gives out no more rows than that, with distinct ids: the
+        # insert cannot answer DUPLICATE or FULL, and reading its status back would wait for the stream
+        self.table.insert([ids[k] for k in take], np.asarray(rows, dtype=np.int32), stream=stream)
+        return status
+
+    def remove(self, link_ids, stream=None):
+        """Remove links (the watchdog's timeout, or after an ACTIVE state was
+        read back) and free their rows; the rows' private bytes are cleared.
+        Returns the (n,) int32 numpy status: device.LINK_OK or LINK_MISSING."""
+        ids = [bytes(i) for i in link_ids]
+        status = np.full(len(ids), 3, dtype=np.int32)
+        rows, gone = [], []
+        for k, i in enumerate(ids):
+            row = self._row.pop(i, None)
+            if row is not None:
+                status[k] = 0
+                rows.append(row)
+                gone.append(i)
+        if not rows:
+            return status
+        self.table.remove(gone, stream=stream)
+        with _on(stream):
+            r = torch.as_tensor(rows, dtype=torch.int64).to(self.device)
+            self.privates[r] = 0
+            self.sig_seeds[r] = 0
+            self.row_state[r] = CLOSED
+        self._free.extend(rows)
+        return status
+
+    def _read(self, t, link_ids):
+        rows = [self._row[bytes(i)] for i in link_ids]
+        return t.cpu().numpy()[rows] if rows else np.zeros(0, dtype=t.cpu().numpy().dtype)
+
+    def state(self, link_ids):
+        """(n,) uint8 numpy: the links' states (waits for the queued work)."""
+        return self._read(self.row_state, link_ids)
+
+    def hops(self, link_ids):
+        """(expected_hops, rebalanced, mtu) of the links as numpy arrays (waits
+        for the queued work)."""
+        return (self._read(self.expected_hops, link_ids), self._read(self.rebalanced, link_ids),
+                self._read(self.mtu, link_ids))
+
+
+def _unpack_raws(raws, dev):
+    off = np.zeros(len(raws), dtype=np.int64)
+    off[1:] = np.cumsum([len(r) for r in raws])[:-1]
+    pkt = torch.from_numpy(np.frombuffer(b"".join(raws) + b"\0", dtype=np.uint8).copy()).to(dev)
+    pkt_off = torch.from_numpy(off).to(dev)
+    pkt_len = torch.tensor([len(r) for r in raws], dtype=torch.int32, device=dev)
+    fields = torch.empty((len(raws), 96), dtype=torch.uint8, device=dev)
+    _dev.packet_unpack(pkt, pkt_off, pkt_len, fields)
+    return pkt, pkt_off, fields
+
+
+def establish_batch(raws, ks, links, pending, signers=None, seen=None):
+    """The link request proof stage for callers without torch tensors:
+    ``raws`` is a sequence of raw packets as the interface handed them on.
+    Unpacks them and runs device.link_establish against ``ks``, ``links``
+    (:class:`LinkTable`), ``pending`` (:class:`PendingLinks`) and optional
+    ``signers`` and ``seen``.  Returns one dict per packet: ``status``
+    (LRPROOF_*), ``slot`` (or -1) and ``mtu`` (of an activated link, else None)."""
+    dev = links.device
+    raws = [bytes(r) for r in raws]
+    n = len(raws)
+    if n == 0:
+        return []
+    pkt, pkt_off, fields = _unpack_raws(raws, dev)
+    status, slot, mtu = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    _dev.link_establish(ks, links, pending, pkt, pkt_off, fields, status, slot, mtu, signers=signers, seen=seen)
+    status, slot, mtu = (t.cpu().numpy() for t in (status, slot, mtu))
+    return [{"status": int(status[i]), "slot": int(slot[i]),
+             "mtu": int(mtu[i]) if status[i] == LRPROOF_ACTIVATED else None} for i in range(n)]
+
+
+def pack_link_request(destination_hash, pub, sig_pub, mtu=MTU):
+    """The raw LINKREQUEST packet (Link.py:304-316, Packet.pack): flags 0x02
+    (HEADER_1, broadcast, SINGLE, LINKREQUEST), hops 0, the destination hash,
+    context 0, then the two public keys and, unless ``mtu`` is None, the three
+    signalling bytes."""
+    destination_hash, pub, sig_pub = bytes(destination_hash), bytes(pub), bytes(sig_pub)
+    if len(destination_hash) != LINK_ID_LEN or len(pub) != 32 or len(sig_pub) != 32:
+        raise ValueError("a 16-byte destination hash and two 32-byte public keys")
+    return b"\x02\x00" + destination_hash + b"\x00" + pub + sig_pub + (b"" if mtu is None else signalling_bytes(mtu))
+
+
+def open_requests_batch(destination_hashes, dest_sig_publics, ephemeral_privates, sig_seeds, slots, expected_hops,
+                        mtu=MTU, flags=None, pending=None, device=None):
+    """The initiator's other end: the LINKREQUEST packets that open links to
+    ``destination_hashes`` (16 bytes each), from ``ephemeral_privates`` and
+    ``sig_seeds`` (32 bytes of fresh randomness each, as
+    X25519PrivateKey.generate and Ed25519PrivateKey.generate draw them).  The
+    public keys come from device.x25519 on the base point and
+    device.ed25519_public; ``mtu`` is the next hop's HW_MTU to signal (None:
+    no signalling bytes).  With ``pending`` the links are entered there, with
+    ``dest_sig_publics`` (the destinations' Ed25519 public keys), ``slots``
+    (distinct, as a free list gives them), ``expected_hops`` and ``flags``
+    (signer flags, default 0); where ``pending`` cannot take them all, none is
+    entered and ValueError is raised.  Returns (raws, link_ids)."""
+    dev = pending.device if pending is not None else _torch_device(device)
+    prv = _rows(ephemeral_privates, 32, dev, "ephemeral_privates")
+    seeds = _rows(sig_seeds, 32, dev, "sig_seeds")
+    hashes = [bytes(h) for h in destination_hashes]
+    n = len(hashes)
+    if prv.shape[0] != n or seeds.shape[0] != n:
+        raise ValueError("one ephemeral private key and one seed per destination")
+    if n == 0:
+        return [], []
+    pubs, sig_pubs = torch.empty_like(prv), torch.empty_like(seeds)
+    _dev.x25519(prv, None, pubs)
+    _dev.ed25519_public(seeds, sig_pubs)
+    pubs, sig_pubs = pubs.cpu().numpy(), sig_pubs.cpu().numpy()
+    raws = [pack_link_request(hashes[i], pubs[i].tobytes(), sig_pubs[i].tobytes(), mtu) for i in range(n)]
+    ids = [link_id_from_lr_packet(r) for r in raws]
+    if pending is not None:
+        st = pending.add(ids, prv, dest_sig_publics, seeds, [0] * n if flags is None else flags, slots, expected_hops)
+        if st.any():
+            # nothing half-registered: a request that is sent must have its row, or its proof reads NO_LINK
+            pending.remove([i for i, s in zip(ids, st) if s == 0])
+            raise ValueError("pending has no room for %d of the links, and %d of their ids are pending already"
+                             % (int((st == 2).sum()), int((st == 1).sum())))
+    return raws, ids

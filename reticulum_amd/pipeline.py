@@ -134,7 +134,7 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
 
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
             check_ifac=False, links=None, seen=None, transport_identity=None, transit=None, announces=False,
-            signers=None, receipts=None, accept=None):
+            signers=None, receipts=None, accept=None, establish=None):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -266,7 +266,27 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     the links' host state (watchdog, timeouts, callbacks, the LRRTT that
     activates the link) stay with the caller, keyed by the slot.  Out of scope:
     the initiator side, requests in transit for other nodes, PROVE_APP and the
-    per-interface ingress limits."""
+    per-interface ingress limits.
+
+    ``establish`` (a :class:`reticulum_amd.link.PendingLinks`) validates the
+    link request proofs of the read that answer the node's own link requests
+    (device.link_establish, beside ``accept`` between the packet filter and the
+    link dispatch; Transport.py:2270-2318, Link.py:391-451).  It needs
+    ``links`` and a ``ks`` of 64-byte keys.  A link that comes up enters
+    ``links``, record slot of ``ks`` and, with ``signers``, the slot's rows
+    before the dispatch runs, so a packet on the new link that follows its
+    proof in the same read is decrypted (and proved, where the row's flags say
+    so); one that precedes the proof is dispatched too, the difference
+    ``accept`` has.  With ``seen`` the hashes of the proofs that reached
+    Link.validate_proof enter the list, which the filter left to this stage.
+    The result gains ``lrproof_status`` (int32 per frame, device.LRPROOF_*),
+    ``established_link`` (int32: the slot or -1) and ``link_mtu`` (int32; shared
+    with ``accept``: a frame is a request or a proof).  Sending the LRRTT
+    (link.pack_rtt), timeouts and callbacks stay with the caller, who reads
+    ``establish.state()`` / ``hops()``.  Out of scope: proofs in transit for
+    other nodes."""
+    if establish is not None and (links is None or ks.key_len != 64):
+        raise ValueError("establish needs links and a key set of 64-byte keys")
     if accept is not None:
         get = accept.get if isinstance(accept, dict) else lambda k, d=None: getattr(accept, k, d)
         if links is None or transport_identity is None or ks.key_len != 64:
@@ -346,6 +366,14 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
             device.link_accept(ks, links, acc[0], transport_identity, un, f_off, fields, acc[1], acc[2],
                                linkreq_status, accepted_link, link_id, link_mtu, lr_proofs, lr_proof_len,
                                nh_mtu=acc[3], signers=signers, stream=stream)
+        if establish is not None:
+            lrproof_status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            established_link = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            proof_mtu = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            device.link_establish(ks, links, establish, un, f_off, fields, lrproof_status, established_link, proof_mtu,
+                                  signers=signers, seen=seen, stream=stream)
+            # a frame is a request or a proof: one column for both stages
+            link_mtu = torch.maximum(link_mtu, proof_mtu) if accept is not None else proof_mtu
         tok_off = torch.empty(max_pairs, dtype=torch.int64, device=dev)
         tok_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
         key_idx = None
@@ -387,6 +415,8 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     if accept is not None:
         res.update(linkreq_status=linkreq_status, accepted_link=accepted_link, link_id=link_id, link_mtu=link_mtu,
                    lr_proofs=lr_proofs, lr_proof_len=lr_proof_len)
+    if establish is not None:
+        res.update(lrproof_status=lrproof_status, established_link=established_link, link_mtu=link_mtu)
     return res
 
 
