@@ -45,6 +45,9 @@
  *   rt_keyset_set_rows_x25519  Link.handshake's key into a record of an existing key set  RNS/Link.py:348-361
  *   rt_link_establish  link request proofs        RNS/Transport.py:2270-2318, RNS/Link.py:391-451, 326-333,
  *                      validated (initiator side)  348-361
+ *   rt_destination_deliver  packets for the node's  RNS/Transport.py:2188-2202, RNS/Destination.py:414-429,
+ *                      SINGLE destinations         622-654, RNS/Identity.py:848-898, 942-953,
+ *                      opened and proved           RNS/Packet.py:327-336, 376-381
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
@@ -1012,6 +1015,74 @@ int rt_link_establish(rt_linktable *pending, uint32_t n_rows, const uint8_t *row
                       uint8_t *sg_seeds, uint8_t *sg_publics, uint64_t sg_stride, uint8_t *sg_peer_publics,
                       uint8_t *sg_flags, rt_hashlist *seen, int32_t *status, int32_t *established, int32_t *mtu,
                       void *stream);
+
+/* ---- destination delivery (RNS/Transport.py:2188-2202) -------------------- */
+/* The DATA packets of a read that are addressed to the node's own SINGLE
+ * destinations: opened as Destination.receive and Identity.decrypt open them
+ * (Destination.py:414-429, 622-654; Identity.py:848-898) and, for a PROVE_ALL
+ * destination, proved as Packet.prove does (Packet.py:327-336, 376-381;
+ * Identity.py:942-953), over the records rt_packet_unpack wrote, each packet
+ * read inside pkt + pkt_off[i].  DEVICE pointers; only enqueues.
+ *
+ * The destinations: `dests` maps the 16-byte destination hash to a row
+ * < n_dests; per row the identity's X25519 private key (privates, 32 B), its
+ * hash (identity_hashes, 16 B on words: the HKDF salt of Identity.get_salt),
+ * its Ed25519 seed and public key (32 B each), a flags byte (RT_LINK_PROVE_ALL
+ * | RT_DEST_ENFORCE_RATCHETS; a PROVE_APP or PROVE_NONE destination has no
+ * proof flag) and its ratchet private keys ratchets[ratchet_off[row] ..
+ * ratchet_off[row + 1]) (32 B each, n_ratchets rows in all), newest first as
+ * Destination.ratchets is ordered.
+ *
+ * Record i: RT_DELIVER_NOT_DATA where fields[i].ok is 0, the packet is no DATA
+ * packet or its destination type is LINK; NO_DESTINATION where the hash is not
+ * in the table; TYPE_MISMATCH where it is and the packet's destination type is
+ * not SINGLE (Transport.py:2194); SHORT for data of 32 bytes or fewer
+ * (Identity.py:858).  Otherwise the candidates are the ratchets in order and
+ * then the identity's key (left out with ENFORCE_RATCHETS; none at all opens
+ * nothing), candidate key = Token(hkdf(64, X25519(candidate, data[:32]),
+ * identity hash)) with the exchange X25519PrivateKey.exchange performs (bit
+ * 255 of the peer's value counts), and the first candidate whose tag verifies
+ * over a well-formed token data[32:] (rt_verify_trials' rule) decrypts it:
+ * DELIVERED, or NOT_OPENED where none does or the padding fails under that key.
+ * The first pass keys and tries candidate 0 of every such frame in scratch
+ * records 0 .. ; the second lays the remaining candidates of the frames still
+ * undecided, in stream order, into records max_frames .. max_frames +
+ * retry_trials - 1: only whole frames, and a frame that does not fit is
+ * DEFERRED with every undecided frame behind it, nothing written for them but
+ * deliver_status and destination.
+ *
+ * For DELIVERED and NOT_OPENED frames status[i] and pt_len[i] are the token
+ * decrypt's (RT_ST_*; RT_ST_BAD_HMAC, or TOO_SHORT for a token of 32 bytes or
+ * fewer, where no candidate verified) and pt_off[i] = the token's offset +
+ * pt_shift (0..16), where the plaintext is written into `pt`; for every other
+ * frame the three are left as they are.  destination[i] is the row or -1;
+ * ratchet[i] the rank of the ratchet that opened the frame, -1 for the
+ * identity's key or for nothing.  A DELIVERED frame of a PROVE_ALL destination
+ * has proof_len[i] = 83 (implicit_proof) or 115 and the PROOF packet at proofs
+ * + i*proof_stride (>= 115): 0x03, hops 0, packet hash[:16], context 0,
+ * [packet hash,] signature; elsewhere proof_len[i] = 0 and the row is not
+ * written.  `scratch` is a key set of 64-byte keys with at least max_frames +
+ * retry_trials records, `work` 16-byte aligned device memory of
+ * rt_destination_deliver_workspace_bytes(max_frames, retry_trials); both are the
+ * stage's until the call's work on `stream` has run.  n <= max_frames. */
+#define RT_DEST_ENFORCE_RATCHETS 8u
+#define RT_DELIVER_DELIVERED      0
+#define RT_DELIVER_NOT_DATA       1
+#define RT_DELIVER_NO_DESTINATION 2
+#define RT_DELIVER_TYPE_MISMATCH  3
+#define RT_DELIVER_SHORT          4
+#define RT_DELIVER_NOT_OPENED     5
+#define RT_DELIVER_DEFERRED       6
+uint64_t rt_destination_deliver_workspace_bytes(uint32_t max_frames, uint32_t retry_trials);
+int rt_destination_deliver(rt_linktable *dests, uint32_t n_dests, const uint8_t *privates,
+                           const uint8_t *identity_hashes, const uint8_t *seeds, const uint8_t *publics,
+                           const uint8_t *flags, const uint32_t *ratchet_off, const uint8_t *ratchets,
+                           uint32_t n_ratchets, rt_keyset *scratch, uint32_t max_frames, uint32_t retry_trials,
+                           void *work, uint64_t work_bytes, const uint8_t *pkt, const uint64_t *pkt_off,
+                           const rt_packet_fields *fields, uint32_t n, int implicit_proof, uint32_t pt_shift,
+                           uint8_t *pt, uint64_t *pt_off, uint32_t *pt_len, int32_t *status, int32_t *deliver_status,
+                           int32_t *destination, int32_t *ratchet, uint8_t *proofs, uint64_t proof_stride,
+                           uint32_t *proof_len, void *stream);
 
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from

@@ -45,6 +45,12 @@ signing rows) and ``ReceiptTable`` (Transport.receipts on the device);
 a link proves (Link.py:943-955, 1140-1145, 378-389) and settles the proofs that
 come back (Transport.py:2326-2363, Packet.py:434-459); ``device.link_prove`` and
 ``device.proof_settle`` are the stages alone.
+Packets for the node's own SINGLE destinations (``reticulum_amd.destination``):
+``SingleDestinations`` (keys, ratchets and flags on the device);
+``pipeline.inbound(..., links=table, deliver=destinations)`` opens them (ratchets
+in order, then the identity's key) and proves them for PROVE_ALL destinations
+(Transport.py:2188-2202, Identity.py:848-898, 942-953); ``device.destination_deliver``
+is the stage alone and ``deliver_batch`` the form without tensors.
 
 ``available()`` tells whether the library and a gfx950 device are usable;
 ``reticulum_amd.dropin`` is the import for the reference's one-line swap,
@@ -63,6 +69,8 @@ from . import wire  # noqa: F401
 from . import link  # noqa: F401
 from .link import LinkDestinations, LinkTable, accept_requests_batch, derive_link_keys, link_id_from_lr_packet  # noqa: F401
 from .link import PendingLinks, establish_batch, open_requests_batch, pack_rtt  # noqa: F401
+from . import destination  # noqa: F401
+from .destination import SingleDestinations, deliver_batch  # noqa: F401
 from . import filter  # noqa: F401
 from .filter import PacketHashlist  # noqa: F401
 from . import proof  # noqa: F401

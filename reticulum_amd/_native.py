@@ -122,6 +122,10 @@ SIGNATURES = [
     ("rt_keyset_set_rows_x25519", _int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _u32, _vp]),
     ("rt_link_establish", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp,
                                  _vp, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("rt_destination_deliver_workspace_bytes", _u64, [_u32, _u32]),
+    ("rt_destination_deliver", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64,
+                                      _vp, _vp, _vp, _u32, _int, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64,
+                                      _vp, _vp]),
     ("rt_packet_pack_headers", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("rt_device_alloc", _vp, [_vp, _u64]),
     ("rt_device_free", None, [_vp, _vp]),

@@ -45,7 +45,7 @@
 // The lists' order depends on the scheduling; results are scattered by record
 // index, so nothing the caller sees depends on it.
 #include "table_device.h"
-#include "ed25519_device.h"
+#include "prove_device.h"
 
 namespace rnstok {
 
@@ -99,17 +99,7 @@ __global__ void __launch_bounds__(PROOF_THREADS, 2) k_prove_sign(const ProveArgs
     uint32_t sig[16];
     ifac_sign_words(sig, a.seeds + key, a.publics + key, f.packet_hash, HASH);
     uint8_t *row = a.proofs + (uint64_t)i * a.proof_stride;
-    row[0] = 0x0F;
-    row[1] = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; ++k) row[2 + k] = f.destination_hash[k];
-    row[18] = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < HASH; ++k) row[PROOF_HEADER + k] = f.packet_hash[k];
-    // byte k of the signature with a constant k (a computed word index would put sig in scratch)
-#pragma unroll
-    for (uint32_t k = 0; k < SIGNATURE; ++k)
-        row[PROOF_HEADER + HASH + k] = (uint8_t)(sig[k >> 2] >> (8 * (k & 3)));
+    prove_write<HASH>(row, 0x0F, f.destination_hash, f.packet_hash, sig);
 }
 
 __device__ __forceinline__ uint32_t le32(const uint8_t *p) {

@@ -412,6 +412,45 @@ struct LrProofArgs {
 uint64_t lrproof_workspace_bytes(uint32_t n, uint32_t n_rows);
 hipError_t launch_link_establish(const LrProofArgs &a, hipStream_t s);
 
+// Destination delivery (destination_kernels.hip): the records rt_packet_unpack
+// wrote, the node's SINGLE destinations (a link table from destination hash to
+// row, beside the rows' keys, flags and ratchets), and the scratch key records
+// the candidates' keys go into: rows 0 .. max_frames-1 for the first pass,
+// max_frames .. max_frames+retry-1 for the second.  `work` is
+// deliver_workspace_bytes(max_frames, retry) of device memory (destination_host.h)
+// the launch may use until it has run.
+struct DeliverArgs {
+    const uint8_t *pkt;
+    const uint64_t *pkt_off;
+    const uint8_t *fields;         // n rt_packet_fields records
+    LinkTab dests;                 // destination hash -> row
+    uint32_t n_dests;
+    const uint8_t *privates;       // n_dests x 32 B: the identities' X25519 private keys
+    const uint8_t *id_hashes;      // n_dests x 16 B: the identities' hashes, the HKDF salt
+    const uint8_t *seeds, *publics;    // n_dests x 32 B each: Ed25519
+    const uint8_t *flags;          // n_dests: RT_LINK_PROVE_ALL | RT_DEST_ENFORCE_RATCHETS
+    const uint32_t *ratchet_off;   // n_dests + 1
+    const uint8_t *ratchets;       // total x 32 B, each destination's newest first
+    uint32_t n_ratchets;           // rows `ratchets` holds: an offset past them is never followed
+    uint32_t *rec;                 // the scratch key set's records
+    const uint8_t *sbox;
+    uint32_t max_frames, retry;
+    uint32_t implicit_proof, pt_shift;
+    uint8_t *pt;
+    uint64_t *pt_off;
+    uint32_t *pt_len;
+    int32_t *status;               // the token status
+    int32_t *deliver_status, *destination, *ratchet;
+    uint8_t *proofs;               // 83 or 115 bytes at proofs + i*proof_stride where proof_len[i] says so
+    uint64_t proof_stride;
+    uint32_t *proof_len;
+    uint32_t *work;
+    uint32_t n;
+    unsigned long long *clk;       // the decrypt's launch-clock words, or null
+};
+struct SpareQueue;                 // below: the decrypt's chunk counters
+hipError_t launch_destination_deliver(const DeliverArgs &a, int n_cu, SpareQueue *spare, hipStream_t s);
+
 // Packet hash list and packet filter (filter_kernels.hip; the layout is
 // described there).  Two generations of slot words and 32-byte hashes; which
 // of them is the current one is a word in device memory that every kernel reads.

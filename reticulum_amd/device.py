@@ -1145,6 +1145,71 @@ def link_establish(ks: KeySet, links, pending, pkt, pkt_off, fields, status, est
         _stream(stream, pkt.device)))
 
 
+# Destination delivery (destination_kernels.hip): ``destinations`` is a
+# reticulum_amd.destination.SingleDestinations.
+
+DELIVER_DELIVERED, DELIVER_NOT_DATA, DELIVER_NO_DESTINATION, DELIVER_TYPE_MISMATCH = 0, 1, 2, 3   # RT_DELIVER_*
+DELIVER_SHORT, DELIVER_NOT_OPENED, DELIVER_DEFERRED = 4, 5, 6
+DEST_ENFORCE_RATCHETS = 8    # RT_DEST_ENFORCE_RATCHETS, beside LINK_PROVE_ALL
+DEST_PROOF_IMPLICIT_LEN, DEST_PROOF_EXPLICIT_LEN = 83, 115
+
+
+def destination_deliver(destinations, pkt, pkt_off, fields, pt, pt_off, pt_len, status, deliver_status, destination,
+                        ratchet, dest_proofs, dest_proof_len, implicit_proof=True, pt_shift=0, stream=None):
+    """The DATA packets for the node's own SINGLE destinations
+    (Transport.py:2188-2202, Destination.py:414-429, 622-654,
+    Identity.py:848-898, 942-953) over packet_unpack's records, each packet read
+    inside pkt[pkt_off[i]:]; at most destinations.max_frames records.
+
+    deliver_status[i] ((n,) int32) is DELIVER_NOT_DATA (not ok, no DATA packet,
+    or destination type LINK), NO_DESTINATION, TYPE_MISMATCH (the hash is a
+    destination's, the packet's type is not SINGLE), SHORT (data of 32 bytes or
+    fewer), DELIVERED, NOT_OPENED (no candidate key opens the token, or the
+    padding fails under the one that verifies) or DEFERRED (the frame's
+    remaining candidates did not fit ``retry_trials`` after its first candidate
+    failed; so is every undecided frame behind it, and nothing else is written
+    for them).  destination[i] is the row or -1 and ratchet[i] the rank of the
+    ratchet that opened the frame (-1: the identity's key, or nothing).  For
+    DELIVERED and NOT_OPENED frames status[i] and pt_len[i] are the token
+    decrypt's and the plaintext lies at pt[pt_off[i]:], pt_off[i] ((n,) int64,
+    written for these frames) = the token's offset + ``pt_shift``; the three
+    are left alone elsewhere.  A DELIVERED frame of a PROVE_ALL destination has
+    dest_proof_len[i] = 83 (``implicit_proof``) or 115 and the PROOF packet in
+    row i of dest_proofs ((n, >=115) uint8 at any row stride); elsewhere the
+    length is 0 and the row untouched.  Nothing is synchronised, and neither
+    shared secrets nor derived keys leave the device."""
+    n = _check_fields(fields)
+    d = destinations
+    _check_u8(pkt, pt, dest_proofs)
+    for name, t in (("pkt", pkt), ("pt", pt)):
+        if t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{name} must be a flat contiguous uint8 buffer in device memory")
+    _check_i64(n, pkt_off=pkt_off, pt_off=pt_off)
+    _check_i32(n, pt_len=pt_len, status=status, deliver_status=deliver_status, destination=destination,
+               ratchet=ratchet, dest_proof_len=dest_proof_len)
+    if any(t is None for t in (pkt_off, pt_off, pt_len, status, deliver_status, destination, ratchet, dest_proof_len)):
+        raise ValueError("pkt_off, pt_off, pt_len, status, deliver_status, destination, ratchet and dest_proof_len "
+                         "are required")
+    _check_rows("dest_proofs", dest_proofs, n, DEST_PROOF_EXPLICIT_LEN)
+    if n > d.max_frames:
+        raise ValueError(f"the destinations' scratch serves {d.max_frames} frames per call, got {n}")
+    if not 0 <= int(pt_shift) <= 16:
+        raise ValueError("pt_shift is 0 .. 16")
+    _same_device(pkt.device, pkt_off, fields, pt, pt_off, pt_len, status, deliver_status, destination, ratchet,
+                 dest_proofs, dest_proof_len, d.privates, d.identity_hashes, d.seeds, d.publics, d.flags,
+                 d.ratchet_off, d.ratchets, d.work)
+    if n == 0:
+        return
+    _order_after_current(stream, d.ratchets, d.ratchet_off)
+    _native.check(_native.load().rt_destination_deliver(
+        d.table.handle, d.n, _p(d.privates), _p(d.identity_hashes), _p(d.seeds), _p(d.publics), _p(d.flags),
+        _p(d.ratchet_off), _p(d.ratchets), d.ratchets.shape[0], d.scratch.handle, d.max_frames, d.retry_trials,
+        _p(d.work), d.work_bytes, _p(pkt), _p(pkt_off), _p(fields), n, 1 if implicit_proof else 0, int(pt_shift),
+        _p(pt), _p(pt_off), _p(pt_len), _p(status), _p(deliver_status), _p(destination), _p(ratchet),
+        _p_rows(dest_proofs), max(dest_proofs.stride(0), DEST_PROOF_EXPLICIT_LEN), _p(dest_proof_len),
+        _stream(stream, pkt.device)))
+
+
 def ifac_mask(pkt, pkt_off, pkt_len, ifac, ifac_key, out, out_off, stream=None):
     """Transport.transmit's IFAC step (Transport.py:1069-1101): packet i plus
     its access code ifac[i] (n, ifac_size) -> pkt_len[i] + ifac_size masked

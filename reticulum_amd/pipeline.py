@@ -24,6 +24,8 @@ Inbound, as the interface's read loop hands frames to Transport:
     packets proved           Link.py:943-955, 1140-1145, 378-389 (with signers)
     link requests answered   Transport.py:2127-2158, Link.py:186-227, 336-376
                              (with accept, between the filter and the dispatch)
+    packets for the node's   Transport.py:2188-2202, Identity.py:848-898, 942-953
+    SINGLE destinations      (with deliver: opened and proved, after the decrypt)
 
 Every stage is one of reticulum_amd.device's kernels, the rearranging of
 offsets and lengths between them included (frames_compact, token_spans), and
@@ -134,7 +136,8 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
 
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
             check_ifac=False, links=None, seen=None, transport_identity=None, transit=None, announces=False,
-            signers=None, receipts=None, accept=None, establish=None):
+            signers=None, receipts=None, accept=None, establish=None, deliver=None,
+            implicit_proof=True):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -284,7 +287,30 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     with ``accept``: a frame is a request or a proof).  Sending the LRRTT
     (link.pack_rtt), timeouts and callbacks stay with the caller, who reads
     ``establish.state()`` / ``hops()``.  Out of scope: proofs in transit for
-    other nodes."""
+    other nodes.
+
+    ``deliver`` (a :class:`reticulum_amd.destination.SingleDestinations`) opens
+    and proves the DATA packets of the read that are addressed to the node's
+    own SINGLE destinations (device.destination_deliver, after the decrypt and
+    the link proofs; Transport.py:2188-2202, Identity.py:848-898, 942-953).  It
+    needs ``links`` (which may be an empty table: without one every packet is
+    decrypted under key 0) and ``max_pairs`` <= ``deliver.max_frames``.  It
+    touches only frames the link dispatch leaves at route 0: a frame an
+    earlier stage dropped (a forged access code, a replay) has ok = 0 and reads
+    DELIVER_NOT_DATA, and the link frames' ``status``, ``pt_len``, ``route``,
+    ``key_idx`` and proofs are what they are without ``deliver``.  The result
+    gains ``deliver_status`` (int32 per frame, device.DELIVER_*),
+    ``destination`` (int32: the row or -1), ``ratchet`` (int32: the rank of the
+    ratchet that opened the frame, -1 for the identity's key or for nothing;
+    the caller derives latest_ratchet_id from it), ``dest_proofs`` (uint8,
+    max_pairs x 128: the PROOF packet, 83 bytes with ``implicit_proof`` and 115
+    without) and ``dest_proof_len``; ``pt_off``, ``pt_len`` and ``status``
+    become valid for the DELIVERED and NOT_OPENED frames.  GROUP and PLAIN
+    destinations, the PROVE_APP callback (its frames are delivered, not
+    proved), the ratchet reload-and-retry, ratchet rotation, DEFERRED frames,
+    sending the proof rows and the receive callbacks stay with the caller."""
+    if deliver is not None and (links is None or max_pairs > deliver.max_frames):
+        raise ValueError("deliver needs links (an empty table will do) and max_pairs <= deliver.max_frames")
     if establish is not None and (links is None or ks.key_len != 64):
         raise ValueError("establish needs links and a key set of 64-byte keys")
     if accept is not None:
@@ -399,6 +425,17 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
             proofs = torch.empty((max_pairs, device.LINE), dtype=torch.uint8, device=dev)
             proof_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
             device.link_prove(fields, route, link, status, signers, proofs, proof_len, stream=stream)
+        if deliver is not None:
+            deliver_status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            destination = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            ratchet = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            dest_proofs = torch.empty((max_pairs, device.LINE), dtype=torch.uint8, device=dev)
+            dest_proof_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            if not pt_shift:
+                pt_off = pt_off.clone()        # tok_off itself stays the spans'
+            device.destination_deliver(deliver, un, f_off, fields, pt, pt_off, pt_len, status, deliver_status,
+                                       destination, ratchet, dest_proofs, dest_proof_len,
+                                       implicit_proof=implicit_proof, pt_shift=pt_shift, stream=stream)
     res = {"pt": pt, "pt_off": pt_off, "pt_len": pt_len, "status": status, "ifac": ifac,
            "ifac_status": ifac_status, "fields": fields, "frame_pair": frame_pair, "n_frames": n_frames,
            "frame_status": d_st, "frame_len": d_len, "counts": counts}
@@ -417,6 +454,9 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
                    lr_proofs=lr_proofs, lr_proof_len=lr_proof_len)
     if establish is not None:
         res.update(lrproof_status=lrproof_status, established_link=established_link, link_mtu=link_mtu)
+    if deliver is not None:
+        res.update(deliver_status=deliver_status, destination=destination, ratchet=ratchet, dest_proofs=dest_proofs,
+                   dest_proof_len=dest_proof_len)
     return res
 
 
