@@ -48,6 +48,9 @@
  *   rt_destination_deliver  packets for the node's  RNS/Transport.py:2188-2202, RNS/Destination.py:414-429,
  *                      SINGLE destinations         622-654, RNS/Identity.py:848-898, 942-953,
  *                      opened and proved           RNS/Packet.py:327-336, 376-381
+ *   rt_receipt_store_keyed /  proofs for packets    RNS/Transport.py:2326-2363 (packet.link unset),
+ *   rt_destination_proof_settle  sent to SINGLE    RNS/Packet.py:480-524 (validate_proof), 376-381
+ *                      destinations, settled
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
@@ -1083,6 +1086,73 @@ int rt_destination_deliver(rt_linktable *dests, uint32_t n_dests, const uint8_t 
                            uint8_t *pt, uint64_t *pt_off, uint32_t *pt_len, int32_t *status, int32_t *deliver_status,
                            int32_t *destination, int32_t *ratchet, uint8_t *proofs, uint64_t proof_stride,
                            uint32_t *proof_len, void *stream);
+
+/* ---- proofs for packets sent to SINGLE destinations (Transport.py:2326-2363, Packet.py:480-524) */
+/* The other end of rt_destination_deliver's proof rows: the PROOF packets of a
+ * read that are neither link request proofs nor resource proofs and arrive on
+ * no active link, settled against the receipts of the packets this node sent
+ * to SINGLE destinations (PacketReceipt.validate_proof), over the records
+ * rt_packet_unpack wrote, each proof read inside pkt + pkt_off[i], as if the
+ * packets came one after another in index order.  DEVICE pointers; only
+ * enqueues.
+ *
+ * Keyed receipts are a receipt table (above) with two more arrays by id, the
+ * caller's: receipt_keys (max_receipts x 32 bytes), the Ed25519 public key of
+ * the identity the packet went to (Identity.get_public_key()[32:64]), and
+ * receipt_keyed (max_receipts bytes), 0 for a receipt without an identity (one
+ * sent on a link), which no proof of this kind delivers.  Adding receipts is
+ * rt_linktable_insert (packet hash[:16], id) followed by rt_receipt_store_keyed
+ * over the same batch and the status the insert wrote: hash, key (keys n x 32,
+ * or NULL: keyed 0) and keyed are written where status[i] is RT_LINK_OK and
+ * ids[i] < max_receipts, so a duplicate leaves the earlier entry untouched.
+ *
+ * dproof_status[i], the first rule that applies:
+ *   RT_DPROOF_NOT_PROOF      fields[i].ok == 0, not a PROOF, or context LRPROOF
+ *                            (0xFF) or RESOURCE_PRF (0x05);
+ *   RT_DPROOF_ON_LINK        destination type LINK and link[i] in 0 .. n_links-1:
+ *                            rt_proof_settle's business.  link NULL: no link is
+ *                            active and this never applies;
+ *   RT_DPROOF_BAD_LENGTH     data of neither 64 nor 96 bytes;
+ *   RT_DPROOF_NO_RECEIPT     explicit (96): no keyed receipt holds data[:32],
+ *                            compared in full, or a lower index of the batch
+ *                            delivered it.  Implicit (64): every keyed receipt
+ *                            was tried and none validated, or the one that
+ *                            would have was delivered to a lower index;
+ *   RT_DPROOF_BAD_SIGNATURE  explicit only: the receipt is there and data[32:96]
+ *                            is not its key's signature of its hash, as
+ *                            rt_ed25519_verify judges;
+ *   RT_DPROOF_DEFERRED       implicit: the proof had to be tried against the
+ *                            whole table and its frame did not fit scan_trials;
+ *                            nothing else is written for it;
+ *   RT_DPROOF_DELIVERED      receipt[i] is the receipt's id and the entry has
+ *                            left the table inside the call.
+ * receipt[i] is -1 for every other status.  An implicit proof is first tried
+ * against the keyed receipt at its own destination hash (an honest proof is
+ * addressed to hash[:16] of the packet it proves): one verification.  The
+ * proofs that fail there or find no keyed receipt there, the strays, are
+ * ranked in index order, and stray r is tried against all L live keyed
+ * receipts when (r + 1) * L <= scan_trials: only whole frames, and every stray
+ * behind the first that does not fit is DEFERRED.  With L = 0 every stray is
+ * NO_RECEIPT.  The lowest index that validates a receipt is delivered whatever
+ * the scheduling.  `work` is 16-byte aligned device memory of
+ * rt_destination_proof_workspace_bytes(n, max_receipts), the stage's until the
+ * call's work on `stream` has run. */
+#define RT_DPROOF_DELIVERED     0
+#define RT_DPROOF_NOT_PROOF     1
+#define RT_DPROOF_ON_LINK       2
+#define RT_DPROOF_BAD_LENGTH    3
+#define RT_DPROOF_NO_RECEIPT    4
+#define RT_DPROOF_BAD_SIGNATURE 5
+#define RT_DPROOF_DEFERRED      6
+uint64_t rt_destination_proof_workspace_bytes(uint32_t n, uint32_t max_receipts);
+int rt_receipt_store_keyed(rt_linktable *receipts, uint8_t *receipt_hashes, uint8_t *receipt_keys,
+                           uint8_t *receipt_keyed, uint32_t max_receipts, const uint8_t *hashes, const uint8_t *keys,
+                           const uint32_t *ids, const int32_t *status, uint32_t n, void *stream);
+int rt_destination_proof_settle(rt_linktable *receipts, const uint8_t *receipt_hashes, const uint8_t *receipt_keys,
+                                const uint8_t *receipt_keyed, uint32_t max_receipts, uint32_t scan_trials, void *work,
+                                uint64_t work_bytes, const uint8_t *pkt, const uint64_t *pkt_off,
+                                const rt_packet_fields *fields, const int32_t *link, uint32_t n_links,
+                                int32_t *dproof_status, int32_t *receipt, uint32_t n, void *stream);
 
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from

@@ -51,6 +51,12 @@ Packets for the node's own SINGLE destinations (``reticulum_amd.destination``):
 in order, then the identity's key) and proves them for PROVE_ALL destinations
 (Transport.py:2188-2202, Identity.py:848-898, 942-953); ``device.destination_deliver``
 is the stage alone and ``deliver_batch`` the form without tensors.
+The proofs that come back for packets sent to SINGLE destinations
+(``reticulum_amd.proof.DestinationReceipts``: the receipts with the recipient
+identities' keys): ``pipeline.inbound(..., destination_receipts=t)`` settles
+explicit and implicit proofs (Transport.py:2326-2363, Packet.py:480-524);
+``device.destination_proof_settle`` is the stage alone and
+``settle_destination_proofs_batch`` the form without tensors.
 
 ``available()`` tells whether the library and a gfx950 device are usable;
 ``reticulum_amd.dropin`` is the import for the reference's one-line swap,
@@ -70,11 +76,11 @@ from . import link  # noqa: F401
 from .link import LinkDestinations, LinkTable, accept_requests_batch, derive_link_keys, link_id_from_lr_packet  # noqa: F401
 from .link import PendingLinks, establish_batch, open_requests_batch, pack_rtt  # noqa: F401
 from . import destination  # noqa: F401
-from .destination import SingleDestinations, deliver_batch  # noqa: F401
+from .destination import SingleDestinations, deliver_batch, settle_destination_proofs_batch  # noqa: F401
 from . import filter  # noqa: F401
 from .filter import PacketHashlist  # noqa: F401
 from . import proof  # noqa: F401
-from .proof import LinkSigners, ReceiptTable  # noqa: F401
+from .proof import DestinationReceipts, LinkSigners, ReceiptTable  # noqa: F401
 from .token import AES, AES_128_CBC, AES_256_CBC, KeySet, Packed, Token, TOKEN_OVERHEAD, token_len  # noqa: F401
 
 __version__ = "0.1.0"

@@ -26,6 +26,8 @@ RT_ANNOUNCE_BAD_SIGNATURE, RT_ANNOUNCE_BAD_DESTINATION = 3, 4
 RT_LINK_PROVE_ALL, RT_LINK_HAS_CHANNEL = 1, 2
 RT_PROOF_DELIVERED, RT_PROOF_NOT_PROOF, RT_PROOF_NOT_LINK, RT_PROOF_NO_LINK = 0, 1, 2, 3
 RT_PROOF_SHORT, RT_PROOF_NO_RECEIPT, RT_PROOF_BAD_SIGNATURE = 4, 5, 6
+RT_DPROOF_DELIVERED, RT_DPROOF_NOT_PROOF, RT_DPROOF_ON_LINK, RT_DPROOF_BAD_LENGTH = 0, 1, 2, 3
+RT_DPROOF_NO_RECEIPT, RT_DPROOF_BAD_SIGNATURE, RT_DPROOF_DEFERRED = 4, 5, 6
 # the RNSTOK_ABI_VERSION (include/rnstok.h) these bindings are written for;
 # load() refuses any other build of the library
 ABI_VERSION = 3
@@ -126,6 +128,10 @@ SIGNATURES = [
     ("rt_destination_deliver", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64,
                                       _vp, _vp, _vp, _u32, _int, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64,
                                       _vp, _vp]),
+    ("rt_destination_proof_workspace_bytes", _u64, [_u32, _u32]),
+    ("rt_receipt_store_keyed", _int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
+    ("rt_destination_proof_settle", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp,
+                                           _vp, _u32, _vp]),
     ("rt_packet_pack_headers", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("rt_device_alloc", _vp, [_vp, _u64]),
     ("rt_device_free", None, [_vp, _vp]),

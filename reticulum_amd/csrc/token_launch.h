@@ -338,6 +338,33 @@ hipError_t launch_proof_settle(const SettleArgs &a, hipStream_t s);
 hipError_t launch_receipt_store(uint8_t *store, uint32_t max_receipts, const uint8_t *hashes, const uint32_t *ids,
                                 const int32_t *status, uint32_t n, hipStream_t s);
 
+// Proofs for packets sent to SINGLE destinations (dproof_kernels.hip): the
+// receipts as above, beside them the key each is verified under (keys, 32 B by
+// id) and whether it has one (keyed, one byte by id).  `link` may be null: no
+// link is active.  `work` is dproof_workspace_bytes(n, t.cap, max_receipts)
+// (dproof_host.h) of 16-byte aligned device memory.
+struct DproofArgs {
+    LinkTab t;                     // the receipts: hash[:16] -> id
+    const uint8_t *hashes;         // max_receipts x 32 B, by id
+    const uint8_t *keys;           // max_receipts x 32 B, by id
+    const uint8_t *keyed;          // max_receipts
+    uint32_t max_receipts;
+    const uint8_t *pkt;
+    const uint64_t *pkt_off;
+    const uint8_t *fields;
+    const int32_t *link;
+    uint32_t n_links;
+    uint32_t scan_trials;
+    int32_t *status, *receipt;
+    uint32_t *work;
+    uint32_t n;
+};
+hipError_t launch_dproof_settle(const DproofArgs &a, hipStream_t s);
+// as launch_receipt_store, and key_store[ids[i]] = keys[i], keyed[ids[i]] = 1 (keys null: keyed 0)
+hipError_t launch_receipt_store_keyed(uint8_t *store, uint8_t *key_store, uint8_t *keyed, uint32_t max_receipts,
+                                      const uint8_t *hashes, const uint8_t *keys, const uint32_t *ids,
+                                      const int32_t *status, uint32_t n, hipStream_t s);
+
 // Link requests (linkreq_kernels.hip): the records rt_packet_unpack wrote, the
 // node's destinations (a link table from destination hash to row, beside the
 // rows' seeds, publics and flags), the link table and key records the accepted

@@ -11,6 +11,9 @@ Identity.py:942-953).  :class:`SingleDestinations` keeps what that needs in
 device memory, ``pipeline.inbound(..., deliver=destinations)`` /
 ``device.destination_deliver`` run it over the frames of a read, and
 :func:`deliver_batch` is the form for callers without tensors.
+:func:`settle_destination_proofs_batch` is that form for the other end: the
+proofs that come back for packets this node sent to SINGLE destinations
+(reticulum_amd.proof.DestinationReceipts).
 """
 import numpy as np
 
@@ -180,3 +183,24 @@ def deliver_batch(raws, destinations, implicit_proof=True):
              for i in range(n)]
     out_proofs = [proofs[i, :plen[i]].tobytes() if plen[i] else None for i in range(n)]
     return plain, dstatus, dest, ratchet, out_proofs
+
+
+def settle_destination_proofs_batch(raws, receipts):
+    """The proofs for packets sent to SINGLE destinations, for callers without
+    torch tensors: ``raws`` is a sequence of raw packets (byte strings, as the
+    interface handed them on) and ``receipts`` a
+    :class:`reticulum_amd.proof.DestinationReceipts`.  Unpacks them and runs
+    device.destination_proof_settle with no link active.  Returns ``(status,
+    receipt)``, (n,) int32 numpy arrays: device.DPROOF_* and the delivered
+    receipt's id (which has left the table) or -1."""
+    dev = receipts.device
+    raws = [bytes(r) for r in raws]
+    n = len(raws)
+    if n == 0:
+        z = np.zeros(0, dtype=np.int32)
+        return z, z.copy()
+    pkt, pkt_off, fields = _unpack_raws(raws, dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    receipt = torch.zeros(n, dtype=torch.int32, device=dev)
+    _dev.destination_proof_settle(pkt, pkt_off, fields, receipts, status, receipt)
+    return status.cpu().numpy(), receipt.cpu().numpy()

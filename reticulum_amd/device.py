@@ -964,6 +964,85 @@ def proof_settle(pkt, pkt_off, fields, link, signers, receipts, proof_status, re
                                                  _p(receipt), n, _stream(stream, pkt.device)))
 
 
+# Proofs for packets sent to SINGLE destinations (dproof_kernels.hip):
+# ``receipts`` is a reticulum_amd.proof.DestinationReceipts.
+
+DPROOF_DELIVERED, DPROOF_NOT_PROOF, DPROOF_ON_LINK, DPROOF_BAD_LENGTH = 0, 1, 2, 3      # RT_DPROOF_*
+DPROOF_NO_RECEIPT, DPROOF_BAD_SIGNATURE, DPROOF_DEFERRED = 4, 5, 6
+
+
+def _check_keyed_receipts(r):
+    m = r.max_receipts
+    _check_u8(r.hashes, r.keys, r.keyed)
+    for name, t, shape in (("hashes", r.hashes, (m, 32)), ("keys", r.keys, (m, 32)), ("keyed", r.keyed, (m,))):
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"receipts.{name} must be a contiguous {shape} uint8 tensor")
+
+
+def receipt_store_keyed(receipts, hashes, keys, ids, status, stream=None):
+    """The second half of DestinationReceipts.add: where the insert's status[i]
+    is LINK_OK, receipts.hashes[ids[i]] = hashes[i] ((n, 32) uint8),
+    receipts.keys[ids[i]] = keys[i] ((n, 32) uint8) and receipts.keyed[ids[i]]
+    = 1; with ``keys`` None the key row is left alone and keyed is 0."""
+    n = _packet_hashes(hashes)
+    _check_i32(n, ids=ids, status=status)
+    if ids is None or status is None:
+        raise ValueError("ids and status are required")
+    if keys is not None:
+        _check_u8(keys)
+        if keys.dim() != 2 or tuple(keys.shape) != (n, 32) or not keys.is_contiguous():
+            raise ValueError(f"keys must be a contiguous ({n}, 32) uint8 tensor")
+    _check_keyed_receipts(receipts)
+    _same_device(hashes.device, keys, ids, status, receipts.hashes, receipts.keys, receipts.keyed)
+    _native.check(_native.load().rt_receipt_store_keyed(receipts.handle, _p(receipts.hashes), _p(receipts.keys),
+                                                        _p(receipts.keyed), receipts.max_receipts, _p(hashes),
+                                                        _p(keys), _p(ids), _p(status), n,
+                                                        _stream(stream, hashes.device)))
+
+
+def destination_proof_settle(pkt, pkt_off, fields, receipts, dproof_status, receipt, link=None, n_links=0,
+                             stream=None):
+    """Transport.inbound's PROOF handling for a proof that arrives on no active
+    link (Transport.py:2326-2363, PacketReceipt.validate_proof,
+    Packet.py:480-524) over packet_unpack's records, each proof read inside its
+    packet pkt[pkt_off[i]:], as if the packets came one after another in index
+    order.  ``receipts`` is a DestinationReceipts; ``link`` is link_spans'
+    ((n,) int32) with ``n_links`` the number of active links, or None: no link
+    is active.  dproof_status[i] ((n,) int32) is DPROOF_NOT_PROOF (not ok, no
+    PROOF, or context LRPROOF / RESOURCE_PRF), DPROOF_ON_LINK (destination type
+    LINK and 0 <= link[i] < n_links: proof_settle's), DPROOF_BAD_LENGTH (data
+    of neither 64 nor 96 bytes), DPROOF_NO_RECEIPT (explicit: no keyed receipt
+    holds data[:32]; implicit: no keyed receipt validates; either: a lower
+    index of the batch delivered it), DPROOF_BAD_SIGNATURE (explicit only),
+    DPROOF_DEFERRED (an implicit proof that had to be tried against the whole
+    table and whose frame did not fit receipts.scan_trials, as every such
+    proof behind it) or DPROOF_DELIVERED; receipt[i] ((n,) int32) is the
+    delivered receipt's id, which leaves the table inside the call, and -1
+    elsewhere.  Nothing is synchronised."""
+    n = _check_fields(fields)
+    _check_u8(pkt)
+    if pkt.dim() != 1 or not pkt.is_cuda or not pkt.is_contiguous():
+        raise ValueError("pkt must be a flat contiguous uint8 buffer in device memory")
+    _check_i64(n, pkt_off=pkt_off)
+    _check_i32(n, link=link, dproof_status=dproof_status, receipt=receipt)
+    if pkt_off is None or dproof_status is None or receipt is None:
+        raise ValueError("pkt_off, dproof_status and receipt are required")
+    n_links = int(n_links) if link is not None else 0
+    if n_links < 0:
+        raise ValueError("n_links is not negative")
+    _check_keyed_receipts(receipts)
+    _same_device(pkt.device, pkt_off, fields, link, dproof_status, receipt, receipts.hashes, receipts.keys,
+                 receipts.keyed)
+    if n == 0:
+        return
+    work = receipts.work_for(n, stream=stream)
+    _same_device(pkt.device, work)
+    _native.check(_native.load().rt_destination_proof_settle(
+        receipts.handle, _p(receipts.hashes), _p(receipts.keys), _p(receipts.keyed), receipts.max_receipts,
+        int(receipts.scan_trials), _p(work), work.numel(), _p(pkt), _p(pkt_off), _p(fields), _p(link), n_links,
+        _p(dproof_status), _p(receipt), n, _stream(stream, pkt.device)))
+
+
 # Link requests (linkreq_kernels.hip): ``destinations`` is a
 # reticulum_amd.link.LinkDestinations, ``links`` a LinkTable, ``signers`` a
 # reticulum_amd.proof.LinkSigners or None.

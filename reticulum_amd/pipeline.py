@@ -137,7 +137,7 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
             check_ifac=False, links=None, seen=None, transport_identity=None, transit=None, announces=False,
             signers=None, receipts=None, accept=None, establish=None, deliver=None,
-            implicit_proof=True):
+            implicit_proof=True, destination_receipts=None):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -308,7 +308,21 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     become valid for the DELIVERED and NOT_OPENED frames.  GROUP and PLAIN
     destinations, the PROVE_APP callback (its frames are delivered, not
     proved), the ratchet reload-and-retry, ratchet rotation, DEFERRED frames,
-    sending the proof rows and the receive callbacks stay with the caller."""
+    sending the proof rows and the receive callbacks stay with the caller.
+
+    ``destination_receipts`` (a
+    :class:`reticulum_amd.proof.DestinationReceipts`) settles the proofs of the
+    read for packets this node sent to SINGLE destinations, explicit and
+    implicit (device.destination_proof_settle, after the packet filter and
+    after the link proofs' settling where that runs; Transport.py:2326-2363,
+    Packet.py:480-524).  It needs neither ``links`` nor ``signers``: with
+    ``links`` a proof of destination type LINK whose link is in the table
+    (with ``signers``: whose ``link`` is below ``signers.n_links``) is left to
+    ``receipts``, without it no link is active.  The result gains
+    ``dproof_status`` (int32 per frame, device.DPROOF_*) and ``dproof_receipt``
+    (int32: the delivered receipt's id, which has left the table, or -1).  The
+    reverse-table transport of proofs, timeouts, culling, delivery callbacks
+    and DPROOF_DEFERRED frames stay with the caller."""
     if deliver is not None and (links is None or max_pairs > deliver.max_frames):
         raise ValueError("deliver needs links (an empty table will do) and max_pairs <= deliver.max_frames")
     if establish is not None and (links is None or ks.key_len != 64):
@@ -415,6 +429,12 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
                 device.proof_settle(un, f_off, fields, link, signers, receipts, proof_status, receipt, stream=stream)
         else:
             device.token_spans(fields, f_off, tok_off, tok_len, stream=stream)
+        if destination_receipts is not None:
+            dproof_status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            dproof_receipt = torch.empty(max_pairs, dtype=torch.int32, device=dev)
+            active = (signers.n_links if signers is not None else 0x7FFFFFFF) if links is not None else 0
+            device.destination_proof_settle(un, f_off, fields, destination_receipts, dproof_status, dproof_receipt,
+                                            link=link if links is not None else None, n_links=active, stream=stream)
         pt = torch.empty_like(un)
         pt_len = torch.empty(max_pairs, dtype=torch.int32, device=dev)
         status = torch.empty(max_pairs, dtype=torch.int32, device=dev)
@@ -449,6 +469,8 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
         res.update(proofs=proofs, proof_len=proof_len)
     if receipts is not None:
         res.update(proof_status=proof_status, receipt=receipt)
+    if destination_receipts is not None:
+        res.update(dproof_status=dproof_status, dproof_receipt=dproof_receipt)
     if accept is not None:
         res.update(linkreq_status=linkreq_status, accepted_link=accepted_link, link_id=link_id, link_mtu=link_mtu,
                    lr_proofs=lr_proofs, lr_proof_len=lr_proof_len)
