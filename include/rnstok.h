@@ -51,6 +51,9 @@
  *   rt_receipt_store_keyed /  proofs for packets    RNS/Transport.py:2326-2363 (packet.link unset),
  *   rt_destination_proof_settle  sent to SINGLE    RNS/Packet.py:480-524 (validate_proof), 376-381
  *                      destinations, settled
+ *   rt_reply_gather /  the replies of a read, sent  RNS/Identity.py:942-953, RNS/Link.py:366-389 (proofs go out
+ *   rt_hdlc_frame_counted /  on the interface the   on the receiving interface), RNS/Transport.py:1069-1104
+ *   rt_reply_remember  frames came in on            (transmit), 1199-1356 (outbound's broadcast), 1343-1345
  *   rt_keyset_create_hkdf  per-packet keying     Identity.py:837-846 (hkdf -> Token(derived_key)),
  *                                                Link.py handshake key derivation
  *   rt_x25519*         X25519 exchange / public key  RNS/Cryptography/X25519.py:49-93, 136-145
@@ -437,6 +440,16 @@ uint32_t rt_resource_hash_split_below(void);
 uint64_t rt_hdlc_frame_workspace_bytes(uint32_t n);
 int rt_hdlc_frame(rt_ctx *ctx, const uint8_t *pkt, const uint64_t *pkt_off, const uint32_t *pkt_len, uint32_t n,
                   uint8_t *out, uint64_t *frame_off, void *workspace, void *stream);
+/* rt_hdlc_frame with the packet count on the device: only the first
+ * m = min(max(*n_dev, 0), n) entries are packets (n_dev: a device int64, e.g.
+ * reply_counts of rt_reply_gather).  Entries m .. n-1 contribute no bytes at
+ * all, whatever their pkt_len and pkt_off hold (they are not read), and
+ * frame_off[i] = frame_off[n] = the total for every i >= m, so
+ * out[0, frame_off[n]) is exactly the m frames.  With *n_dev >= n the result is
+ * rt_hdlc_frame's.  n = 0 writes frame_off[0] = 0.  Same workspace. */
+int rt_hdlc_frame_counted(rt_ctx *ctx, const uint8_t *pkt, const uint64_t *pkt_off, const uint32_t *pkt_len,
+                          uint32_t n, const int64_t *n_dev, uint8_t *out, uint64_t *frame_off, void *workspace,
+                          void *stream);
 /* One pass of the HDLC read loop over buf[0, len) (everything received so
  * far).  For every pair of consecutive 7E flags k, k+1 (at most max_pairs):
  * the frame between them, unescaped with the loop's two replace passes, is
@@ -1153,6 +1166,55 @@ int rt_destination_proof_settle(rt_linktable *receipts, const uint8_t *receipt_h
                                 uint64_t work_bytes, const uint8_t *pkt, const uint64_t *pkt_off,
                                 const rt_packet_fields *fields, const int32_t *link, uint32_t n_links,
                                 int32_t *dproof_status, int32_t *receipt, uint32_t n, void *stream);
+
+/* ---- the replies of a read (Transport.py:1069-1104, 1199-1356; Identity.py:942-953; Link.py:366-389) */
+/* The stages of the inbound path leave what the node has to send as sparse
+ * rows, one per frame with a length column: the LRPROOFs of rt_link_accept, the
+ * LINK PROOFs of rt_link_prove, the PROOFs of rt_destination_deliver.  The
+ * reference transmits each of them on the interface its frame came in on, in
+ * the order of its loop over the frames, so one read has one reply stream.
+ *
+ * rt_reply_gather makes the dense batch.  There are n_sources (1..4) sources
+ * over the same n frames (at most 2^31 - 1); rows, row_stride, row_width and
+ * len are HOST arrays of n_sources entries.  Source s holds for frame k the
+ * len[s][k] bytes at rows[s] + k * row_stride[s] (rows[s], len[s]: DEVICE
+ * pointers; any alignment; row_width[s] <= row_stride[s] is the bytes a row
+ * holds).  A length of 0 means nothing for that frame, and so does any length
+ * outside 1 .. min(128, row_width[s]); no byte at or past a row's length is
+ * read.  The replies are ordered by frame, then by source index, and every
+ * non-zero source of a frame is one reply.  Reply j < written goes to
+ * out + 128 j (out: cap x 128 bytes, 128-byte aligned; the row's bytes past the
+ * reply are zeroed) with reply_len[j], reply_frame[j] (k) and reply_source[j]
+ * (s); reply_counts (device int64[2]) = [written = min(found, cap), found].
+ * Entries written .. cap-1 get reply_len 0, reply_frame -1 and reply_source
+ * 0xFF, and their rows are not written.  n = 0 and cap = 0 are valid.  The
+ * outputs must not overlap the sources.  `workspace` of
+ * rt_reply_gather_workspace_bytes(n, n_sources) bytes (0 for arguments the call
+ * refuses), 8-byte aligned.
+ *
+ * The batch then goes through rt_ifac_sign and rt_ifac_mask where the interface
+ * has access codes, with pkt_off[j] = 128 j (entries past `written` have length
+ * 0 and an offset inside the buffer, which is what those calls need), and
+ * through rt_hdlc_frame_counted with n_dev = reply_counts.
+ *
+ * rt_reply_remember enters the packet hashes of the first
+ * min(reply_counts[0], cap) rows (row j at rows + j * row_stride, row_stride >=
+ * 128; the unmasked packets, as rt_reply_gather wrote them) into the hash
+ * list's current generation, as Transport.outbound does for what it broadcasts
+ * (Transport.py:1343-1345, add_packet_hash) and as rt_hashlist_add does: the
+ * node then drops its own reply when a shared medium echoes it.  The hash is
+ * rt_packet_unpack's; a row too short to be a packet is left out.  The call
+ * takes its place in the list's host order. */
+#define RT_REPLY_LRPROOF    0   /* the source order of the inbound path's stages */
+#define RT_REPLY_LINK_PROOF 1
+#define RT_REPLY_DEST_PROOF 2
+uint64_t rt_reply_gather_workspace_bytes(uint32_t n, uint32_t n_sources);
+int rt_reply_gather(rt_ctx *ctx, uint32_t n_sources, const uint8_t *const *rows, const uint64_t *row_stride,
+                    const uint32_t *row_width, const int32_t *const *len, uint32_t n, uint8_t *out, int32_t *reply_len,
+                    int32_t *reply_frame, uint8_t *reply_source, int64_t *reply_counts, uint32_t cap, void *workspace,
+                    void *stream);
+int rt_reply_remember(rt_hashlist *list, const uint8_t *rows, uint64_t row_stride, const int32_t *reply_len,
+                      const int64_t *reply_counts, uint32_t cap, void *stream);
 
 /* ---- memory helpers (so a non-torch host can drive the device API) ------- */
 /* rt_memcpy_d2h: a pinned (page-locked, mapped) destination, e.g. from

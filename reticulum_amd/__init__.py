@@ -57,6 +57,13 @@ identities' keys): ``pipeline.inbound(..., destination_receipts=t)`` settles
 explicit and implicit proofs (Transport.py:2326-2363, Packet.py:480-524);
 ``device.destination_proof_settle`` is the stage alone and
 ``settle_destination_proofs_batch`` the form without tensors.
+What a read has to send (``pipeline.reply``, or ``pipeline.inbound(...,
+reply=True)``): the link request proofs, link proofs and destination proofs of
+the read gathered in frame order, signed and masked for the interface and
+HDLC-framed, as the byte stream for the socket the read came from
+(Transport.py:1069-1104, 1199-1356); ``device.reply_gather`` and
+``device.hdlc_frame_counted`` are the stages alone and ``reply_batch`` the form
+without tensors.
 
 ``available()`` tells whether the library and a gfx950 device are usable;
 ``reticulum_amd.dropin`` is the import for the reference's one-line swap,
@@ -72,6 +79,7 @@ from .x25519 import exchange, exchange_batch, public_key, public_keys_batch  # n
 from .resource import build_hashmap, get_map_hash, resource_hashmap  # noqa: F401
 from .resource import prepare_resource, resource_hashes, validate_proof, verify_resource  # noqa: F401
 from . import wire  # noqa: F401
+from .wire import reply_batch  # noqa: F401
 from . import link  # noqa: F401
 from .link import LinkDestinations, LinkTable, accept_requests_batch, derive_link_keys, link_id_from_lr_packet  # noqa: F401
 from .link import PendingLinks, establish_batch, open_requests_batch, pack_rtt  # noqa: F401

@@ -28,6 +28,7 @@ RT_PROOF_DELIVERED, RT_PROOF_NOT_PROOF, RT_PROOF_NOT_LINK, RT_PROOF_NO_LINK = 0,
 RT_PROOF_SHORT, RT_PROOF_NO_RECEIPT, RT_PROOF_BAD_SIGNATURE = 4, 5, 6
 RT_DPROOF_DELIVERED, RT_DPROOF_NOT_PROOF, RT_DPROOF_ON_LINK, RT_DPROOF_BAD_LENGTH = 0, 1, 2, 3
 RT_DPROOF_NO_RECEIPT, RT_DPROOF_BAD_SIGNATURE, RT_DPROOF_DEFERRED = 4, 5, 6
+RT_REPLY_LRPROOF, RT_REPLY_LINK_PROOF, RT_REPLY_DEST_PROOF = 0, 1, 2
 # the RNSTOK_ABI_VERSION (include/rnstok.h) these bindings are written for;
 # load() refuses any other build of the library
 ABI_VERSION = 3
@@ -132,6 +133,10 @@ SIGNATURES = [
     ("rt_receipt_store_keyed", _int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("rt_destination_proof_settle", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp,
                                            _vp, _u32, _vp]),
+    ("rt_reply_gather_workspace_bytes", _u64, [_u32, _u32]),
+    ("rt_reply_gather", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    ("rt_hdlc_frame_counted", _int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("rt_reply_remember", _int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
     ("rt_packet_pack_headers", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("rt_device_alloc", _vp, [_vp, _u64]),
     ("rt_device_free", None, [_vp, _vp]),

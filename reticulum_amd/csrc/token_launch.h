@@ -249,6 +249,12 @@ uint64_t hdlc_frame_workspace_bytes(uint32_t n);
 uint64_t hdlc_deframe_workspace_bytes(uint64_t len);
 hipError_t launch_hdlc_frame(const uint8_t *pkt, const uint64_t *off, const uint32_t *len, uint32_t n, uint8_t *out,
                              uint64_t *frame_off, void *ws, hipStream_t s);
+// the same with the packet count on the device: entries at or past min(*n_dev, n) contribute no bytes
+hipError_t launch_hdlc_frame_counted(const uint8_t *pkt, const uint64_t *off, const uint32_t *len, uint32_t n,
+                                     const int64_t *n_dev, uint8_t *out, uint64_t *frame_off, void *ws,
+                                     hipStream_t s);
+// k_scan_parts alone: part[0..nb) scanned in place (exclusive), the sum at part[nb]
+hipError_t launch_scan_parts(uint64_t *part, uint64_t nb, hipStream_t s);
 hipError_t launch_hdlc_deframe(const uint8_t *buf, uint64_t len, uint32_t hw_mtu, uint32_t ifac_size, uint8_t *out,
                                uint64_t *frame_off, uint32_t *frame_len, int32_t *status, uint64_t *counts,
                                uint64_t max_pairs, void *ws, hipStream_t s, uint32_t line_phase = 0xFFFFFFFFu);
@@ -262,6 +268,27 @@ hipError_t launch_token_spans(const void *fields, const uint64_t *pkt_off, uint3
 hipError_t launch_unpack(const uint8_t *pkt, const uint64_t *off, const uint32_t *len, void *fields, uint32_t n,
                          hipStream_t s);
 hipError_t launch_pack_headers(const PackArgs &a, hipStream_t s);
+
+// The send side of a read (reply_kernels.hip; sizes and grids in reply_host.h).
+struct ReplyGatherArgs {
+    const uint8_t *rows[4];        // source s: row k at rows[s] + k * stride[s]
+    uint64_t stride[4];
+    uint32_t width[4];             // bytes a row of source s holds (<= stride[s])
+    const int32_t *len[4];         // 0, or outside 1 .. min(128, width[s]): nothing for that frame
+    uint32_t n_sources;            // 1..4
+    uint32_t n;                    // frames
+    uint8_t *out;                  // cap x 128
+    int32_t *reply_len, *reply_frame;
+    uint8_t *reply_source;
+    int64_t *reply_counts;         // [written, found]
+    uint32_t cap;
+    uint64_t *part;                // the workspace: reply_blocks(n) + 1 words
+};
+hipError_t launch_reply_gather(const ReplyGatherArgs &a, hipStream_t s);
+// hashes[j] (32 B) = the packet hash of row j and mask[j] = 1 for j < min(counts[0], cap) whose length makes a
+// packet; mask[j] = 0 for the others, whose hash is not written
+hipError_t launch_reply_hashes(const uint8_t *rows, uint64_t stride, const int32_t *len, const int64_t *counts,
+                               uint32_t cap, uint8_t *hashes, uint8_t *mask, hipStream_t s);
 
 // Link table and dispatch (link_kernels.hip; the layout is described there).
 struct LinkTab {

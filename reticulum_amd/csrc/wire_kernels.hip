@@ -14,6 +14,7 @@
 //   k_scan_*         exclusive prefix sums (u64) for frame placement
 //   k_hdlc_count     escaped frame length per packet
 //   k_hdlc_write     7E || escape(packet) || 7E at its prefix-sum offset
+//                    (both also COUNTED: the packet count read from the device)
 //   k_flag_local / k_flag_gather    positions of every 7E in a stream
 //   k_hdlc_unescape  one lane per consecutive flag pair: the read loop's two
 //                    bytes.replace passes, check_frame_len, empty-frame skip
@@ -24,6 +25,7 @@
 //   k_token_spans    each unpacked packet's data span (the token)
 #include "token_device.h"
 #include "token_launch.h"
+#include "wire_device.h"
 #include "../../include/rnstok.h"
 
 namespace rnstok {
@@ -32,27 +34,10 @@ namespace {
 
 constexpr uint8_t FLAG = 0x7E;      // HDLC flag; escapes are 7D x^0x20 (eqbytes constants below)
 constexpr uint32_t HEADER_MINSIZE = 19, DST_LEN = 16, PATHFINDER_M = 128;
-constexpr uint32_t SCAN_BLOCK = 1024;
 constexpr uint32_t WAVE_GRID = 16384;        // workgroups of the wave-per-frame kernels (grid-stride beyond)
 
 // ------------------------------------------------------------------ scan --
-
-__device__ uint64_t block_exclusive_scan(uint64_t v, uint64_t *total) {
-    __shared__ uint64_t sh[SCAN_BLOCK];
-    const uint32_t t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < blockDim.x; d <<= 1) {
-        const uint64_t add = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    const uint64_t incl = sh[t];
-    *total = sh[blockDim.x - 1];
-    __syncthreads();
-    return incl - v;
-}
+// (block_exclusive_scan: wire_device.h)
 
 __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_block(const uint64_t *in, uint64_t *out, uint64_t *part,
                                                            uint64_t n) {
@@ -121,27 +106,7 @@ __device__ __forceinline__ uint32_t row_incl_scan16(uint32_t x) {
     x += dpp<0x118>(x);     // row_shr:8
     return x;
 }
-// little-endian word of p[i, i+4), bytes at or past `end` read as 0
-__device__ __forceinline__ uint32_t ld4_upto(const uint8_t *p, uint64_t i, uint64_t end) {
-    if (i + 4 <= end) {
-        uint32_t v;
-        __builtin_memcpy(&v, p + i, 4);
-        return v;
-    }
-    uint32_t v = 0;
-    for (uint32_t k = 0; k < 4; ++k)
-        if (i + k < end) v |= (uint32_t)p[i + k] << (8 * k);
-    return v;
-}
-// 16 bytes of p[i, i+16), bytes at or past `end` read as 0.  (Loading the
-// one or two aligned 16-B blocks that hold a partial window and shifting
-// them into place was slower for framing and deframing alike, round 3:
-// profiles/r03w_tail_ab/.)
-__device__ __forceinline__ u32x4 ld16_upto(const uint8_t *p, uint64_t i, uint64_t end) {
-    if (i + 16 <= end) return ld16(p + i);
-    u32x4 v = {ld4_upto(p, i, end), ld4_upto(p, i + 4, end), ld4_upto(p, i + 8, end), ld4_upto(p, i + 12, end)};
-    return v;
-}
+// (ld4_upto, ld16_upto: wire_device.h)
 __device__ __forceinline__ uint32_t esc_count16(u32x4 v) {
     return __builtin_popcount(escbytes(v.x)) + __builtin_popcount(escbytes(v.y)) + __builtin_popcount(escbytes(v.z)) +
            __builtin_popcount(escbytes(v.w));
@@ -216,26 +181,42 @@ __device__ __forceinline__ void funnel16(uint64_t &lo, uint64_t &hi, uint64_t nl
     }
 }
 
+// COUNTED (rt_hdlc_frame_counted): only the first min(*n_dev, n) entries are
+// packets.  The others get a frame of no bytes at all (flen 0, so their
+// offsets all equal the total) and k_hdlc_write leaves them alone, whatever
+// their len says.  Without COUNTED n_dev is not read.
+template <bool COUNTED>
+__device__ __forceinline__ uint32_t packets_of(const int64_t *n_dev, uint32_t n) {
+    if (!COUNTED) return n;
+    const int64_t c = *n_dev;
+    return c <= 0 ? 0u : (c < (int64_t)n ? (uint32_t)c : n);
+}
+
+template <bool COUNTED>
 __global__ __launch_bounds__(256) void k_hdlc_count(const uint8_t *pkt, const uint64_t *off, const uint32_t *len,
-                                                    uint64_t *flen, uint32_t n) {
+                                                    uint64_t *flen, uint32_t n, const int64_t *n_dev) {
     const uint32_t lane = threadIdx.x & 63u, rl = lane & 15u;
     const uint32_t g0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, ng = (gridDim.x * blockDim.x) >> 6;
+    const uint32_t np = packets_of<COUNTED>(n_dev, n);
     for (uint32_t g = g0; 4ull * g < n; g += ng) {
         const uint32_t i = 4u * g + (lane >> 4);
-        const bool valid = i < n;
-        const uint8_t *p = pkt + (valid ? off[i] : 0);
-        const uint32_t L = valid ? len[i] : 0u;
+        const bool valid = i < n, live = i < np;
+        const uint8_t *p = pkt + (live ? off[i] : 0);
+        const uint32_t L = live ? len[i] : 0u;
         uint32_t extra = 0;
         for (uint32_t b = 16u * rl; b < L; b += 256u) extra += esc_count16(ld16_upto(p, b, L));
         extra = row_sum16(extra);
-        if (rl == 0 && valid) flen[i] = 2ull + L + extra;     // 7E || escape(p) || 7E
+        if (rl == 0 && valid) flen[i] = live ? 2ull + L + extra : 0ull;     // 7E || escape(p) || 7E
     }
 }
 
+template <bool COUNTED>
 __global__ __launch_bounds__(256) void k_hdlc_write(const uint8_t *pkt, const uint64_t *off, const uint32_t *len,
-                                                    const uint64_t *foff, uint8_t *out, uint32_t n) {
+                                                    const uint64_t *foff, uint8_t *out, uint32_t n_all,
+                                                    const int64_t *n_dev) {
     __shared__ SelTables tab;
     fill_sel_tables(&tab);
+    const uint32_t n = packets_of<COUNTED>(n_dev, n_all);
     const uint32_t lane = threadIdx.x & 63u, rl = lane & 15u;
     const uint32_t g0 = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, ng = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t g = g0; 4ull * g < n; g += ng) {
@@ -839,27 +820,7 @@ __global__ __launch_bounds__(256) void k_token_spans(const rt_packet_fields *f, 
 
 // --------------------------------------------------------- packet header --
 
-// SHA-256 over  first || src[0..len): the full 64-B blocks from 16-B loads
-// at src - 1 (that byte is readable: the packet's hop count or the transport
-// id's last byte) with `first` put in front, the last block(s) byte by byte.
-__device__ void sha_prefixed(uint8_t first, const uint8_t *src, uint32_t len, uint32_t out[8]) {
-    uint32_t h[8];
-    sha256_init(h);
-    const uint32_t m = len + 1u;
-    const uint64_t bits = (uint64_t)m * 8u;
-    const uint32_t nfull = m / 64u;
-    for (uint32_t b = 0; b < nfull; ++b) {
-        const uint8_t *B = src - 1 + 64ull * b;
-        uint32_t w[16];
-        sha_units(w, ld16(B), ld16(B + 16), ld16(B + 32), ld16(B + 48));
-        if (b == 0) w[0] = (w[0] & 0x00FFFFFFu) | ((uint32_t)first << 24);
-        sha256_compress(h, w);
-    }
-    // the 0..63 message bytes left
-    sha_tail(h, m - 64u * nfull, bits, PrefixedAt{first, src, 64u * nfull});
-#pragma unroll
-    for (int k = 0; k < 8; ++k) out[k] = h[k];
-}
+// (sha_prefixed, packet_hash_words: wire_device.h)
 
 __global__ __launch_bounds__(256) void k_unpack(const uint8_t *pkt, const uint64_t *off, const uint32_t *len,
                                                 rt_packet_fields *out, uint32_t n) {
@@ -889,9 +850,8 @@ __global__ __launch_bounds__(256) void k_unpack(const uint8_t *pkt, const uint64
             if (f.header_type)
                 for (int k = 0; k < 16; ++k) f.transport_id[k] = raw[2 + k];
             // get_hashable_part: flags & 0x0F || raw[2:] (header 1) or raw[18:] (header 2)
-            const uint32_t from = f.header_type ? DST_LEN + 2u : 2u;
             uint32_t d[8];
-            sha_prefixed(f.flags & 0x0Fu, raw + from, L - from, d);
+            packet_hash_words(raw, L, d);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 f.packet_hash[4 * k] = d[k] >> 24; f.packet_hash[4 * k + 1] = d[k] >> 16;
@@ -950,20 +910,39 @@ static hipError_t launch_scan(const uint64_t *in, uint64_t *out, uint64_t n, uin
     return hipGetLastError();
 }
 
+// the block totals part[0..nb) scanned in place, their sum at part[nb] (reply_kernels.hip places its rows with it)
+hipError_t launch_scan_parts(uint64_t *part, uint64_t nb, hipStream_t s) {
+    hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(SCAN_BLOCK), 0, s, part, nb);
+    return hipGetLastError();
+}
+
 uint64_t hdlc_frame_workspace_bytes(uint32_t n) { return 8ull * n + scan_workspace_bytes(n) + 64; }
 
-hipError_t launch_hdlc_frame(const uint8_t *pkt, const uint64_t *off, const uint32_t *len, uint32_t n, uint8_t *out,
-                             uint64_t *frame_off, void *ws, hipStream_t s) {
-    if (n == 0) return hipSuccess;
+template <bool COUNTED>
+static hipError_t hdlc_frame(const uint8_t *pkt, const uint64_t *off, const uint32_t *len, uint32_t n,
+                             const int64_t *n_dev, uint8_t *out, uint64_t *frame_off, void *ws, hipStream_t s) {
     uint64_t *flen = (uint64_t *)ws;
     uint64_t *part = flen + n;
     // one DPP row per packet: 16 packets per 256-thread workgroup, grid-stride
     const unsigned g = (unsigned)min((uint64_t)(n + 15) / 16, (uint64_t)WAVE_GRID);
-    hipLaunchKernelGGL(k_hdlc_count, dim3(g), dim3(256), 0, s, pkt, off, len, flen, n);
+    hipLaunchKernelGGL(k_hdlc_count<COUNTED>, dim3(g), dim3(256), 0, s, pkt, off, len, flen, n, n_dev);
     hipError_t e = launch_scan(flen, frame_off, n, part, frame_off + n, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_hdlc_write, dim3(g), dim3(256), 0, s, pkt, off, len, frame_off, out, n);
+    hipLaunchKernelGGL(k_hdlc_write<COUNTED>, dim3(g), dim3(256), 0, s, pkt, off, len, frame_off, out, n, n_dev);
     return hipGetLastError();
+}
+
+hipError_t launch_hdlc_frame(const uint8_t *pkt, const uint64_t *off, const uint32_t *len, uint32_t n, uint8_t *out,
+                             uint64_t *frame_off, void *ws, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    return hdlc_frame<false>(pkt, off, len, n, nullptr, out, frame_off, ws, s);
+}
+
+hipError_t launch_hdlc_frame_counted(const uint8_t *pkt, const uint64_t *off, const uint32_t *len, uint32_t n,
+                                     const int64_t *n_dev, uint8_t *out, uint64_t *frame_off, void *ws,
+                                     hipStream_t s) {
+    if (n == 0) return hipMemsetAsync(frame_off, 0, 8, s);        // no frames: the stream is empty
+    return hdlc_frame<true>(pkt, off, len, n, n_dev, out, frame_off, ws, s);
 }
 
 uint64_t hdlc_deframe_workspace_bytes(uint64_t len) {

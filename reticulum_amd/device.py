@@ -5,6 +5,7 @@ buffer is a CUDA(HIP) tensor already resident in HBM, the kernels are
 enqueued on the given stream (default: torch's current stream) and nothing is
 synchronised.  torch is used only for device memory and streams.
 """
+import ctypes
 import threading
 
 import torch
@@ -580,6 +581,29 @@ def hdlc_frame(pkt, pkt_off, pkt_len, out, frame_off, workspace=None, stream=Non
         int(lib.rt_hdlc_frame_workspace_bytes(n)), dtype=torch.uint8, device=pkt.device)
     _native.check(lib.rt_hdlc_frame(_ctx_of(pkt), _p(pkt), _p(pkt_off), _p(pkt_len), n, _p(out), _p(frame_off),
                                     _p(ws), _stream(stream, pkt.device)))
+
+
+def hdlc_frame_counted(pkt, pkt_off, pkt_len, n_dev, out, frame_off, workspace=None, stream=None):
+    """hdlc_frame with the packet count on the device: only the first
+    min(n_dev, n) entries are packets (``n_dev``: an int64 device tensor whose
+    first element is the count, e.g. reply_gather's reply_counts).  The
+    entries past it contribute no bytes whatever their length says, and their
+    frame_off all equal frame_off[n], so out[:frame_off[n]] is exactly the
+    counted frames.  n = 0 gives frame_off[0] = 0."""
+    _check_u8(pkt, out)
+    n = pkt_off.numel()
+    _check_i64(n, pkt_off=pkt_off)
+    _check_i32(n, pkt_len=pkt_len)
+    _check_i64(n + 1, frame_off=frame_off)
+    if n_dev is None or n_dev.dtype != torch.int64 or n_dev.numel() < 1 or not n_dev.is_contiguous():
+        raise ValueError("n_dev must be a contiguous int64 device tensor")
+    lib = _native.load()
+    ws = workspace if workspace is not None else torch.empty(
+        int(lib.rt_hdlc_frame_workspace_bytes(n)), dtype=torch.uint8, device=pkt.device)
+    if ws.numel() < int(lib.rt_hdlc_frame_workspace_bytes(n)):
+        raise ValueError("workspace is smaller than rt_hdlc_frame_workspace_bytes(n)")
+    _native.check(lib.rt_hdlc_frame_counted(_ctx_of(pkt), _p(pkt), _p(pkt_off), _p(pkt_len), n, _p(n_dev), _p(out),
+                                            _p(frame_off), _p(ws), _stream(stream, pkt.device)))
 
 
 def deframe_slots_bytes(nbytes, max_pairs):
@@ -1362,6 +1386,80 @@ def ifac_check(seed, public_key, pkt, pkt_off, pkt_len, ifac, status, stream=Non
     lib = _native.load()
     _native.check(lib.rt_ifac_check(_ctx_of(pkt), _p(seed), _p(public_key), _p(pkt), _p(pkt_off), _p(pkt_len),
                                     _p(ifac), ifac.shape[1], _p(status), n, _stream(stream, pkt.device)))
+
+
+# The replies of a read (reply_kernels.hip)
+
+REPLY_LRPROOF, REPLY_LINK_PROOF, REPLY_DEST_PROOF = 0, 1, 2       # RT_REPLY_* (include/rnstok.h)
+REPLY_MAX_SOURCES = 4
+
+
+def reply_gather(sources, out, reply_len, reply_frame, reply_source, reply_counts, workspace=None, stream=None):
+    """The replies of a read as one dense batch.  ``sources`` is a sequence of
+    one to four (rows, len) pairs over the same n frames: rows an (n, width)
+    uint8 matrix at any row stride >= width, len (n,) int32, where 0 (or
+    anything outside 1 .. min(128, width)) means nothing for that frame.
+    Reply j, in the order of the frames and within a frame of the sources,
+    goes to out[j] (out: (cap, 128) uint8, contiguous; bytes past the reply
+    zeroed) with reply_len[j], reply_frame[j] ((cap,) int32) and
+    reply_source[j] ((cap,) uint8); reply_counts ((2,) int64) = [written =
+    min(found, cap), found].  Entries past ``written`` read 0, -1 and 0xFF and
+    their rows are not written."""
+    sources = list(sources)
+    if not 1 <= len(sources) <= REPLY_MAX_SOURCES:
+        raise ValueError("reply_gather takes 1 to 4 sources")
+    if out.dim() != 2 or out.shape[1] != LINE or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (cap, 128) uint8 matrix")
+    _check_u8(out, reply_source, *[rows for rows, _ in sources])
+    cap = out.shape[0]
+    dev = out.device
+    n = sources[0][1].numel()
+    for rows, ln in sources:
+        _check_i32(n, len=ln)
+        if rows.dim() != 2 or rows.shape[0] != n or rows.shape[1] < 1:
+            raise ValueError(f"every source's rows must be an ({n}, width) uint8 matrix")
+        _same_device(dev, rows, ln)
+    _check_i32(cap, reply_len=reply_len, reply_frame=reply_frame)
+    _check_i64(2, reply_counts=reply_counts)
+    if reply_len is None or reply_frame is None or reply_counts is None or reply_source is None or \
+            reply_source.numel() != cap or not reply_source.is_contiguous():
+        raise ValueError(f"reply_len, reply_frame ({cap},) int32, reply_source ({cap},) uint8 and reply_counts (2,) "
+                         "int64 are required")
+    _same_device(dev, reply_len, reply_frame, reply_source, reply_counts)
+    if cap and out.data_ptr() % LINE:
+        raise ValueError("out must start on a 128-byte line")
+    lib = _native.load()
+    S = len(sources)
+    need = int(lib.rt_reply_gather_workspace_bytes(n, S))
+    if need == 0:
+        raise ValueError("reply_gather takes at most 2**31 - 1 frames")
+    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=dev)
+    if ws.numel() < need or ws.device != dev:
+        raise ValueError("workspace is smaller than rt_reply_gather_workspace_bytes(n, S)")
+    c_rows = (ctypes.c_void_p * S)(*[_p_rows(rows) for rows, _ in sources])
+    c_len = (ctypes.c_void_p * S)(*[_p(ln) for _, ln in sources])
+    c_stride = (ctypes.c_uint64 * S)(*[max(rows.stride(0), rows.shape[1]) for rows, _ in sources])
+    c_width = (ctypes.c_uint32 * S)(*[rows.shape[1] for rows, _ in sources])
+    _native.check(lib.rt_reply_gather(_ctx_of(out), S, c_rows, c_stride, c_width, c_len, n, _p(out), _p(reply_len),
+                                      _p(reply_frame), _p(reply_source), _p(reply_counts), cap, _p(ws),
+                                      _stream(stream, dev)))
+
+
+def reply_remember(lst, packets, reply_len, reply_counts, stream=None):
+    """Enter the packet hashes of the first reply_counts[0] rows of ``packets``
+    ((cap, 128) uint8, as reply_gather wrote them) into the hash list ``lst``
+    (an rt_hashlist handle): Transport.outbound's add_packet_hash for what it
+    broadcasts (Transport.py:1343-1345).  Counted on the device."""
+    _check_u8(packets)
+    if packets.dim() != 2 or packets.shape[1] != LINE or not packets.is_contiguous():
+        raise ValueError("packets must be a contiguous (cap, 128) uint8 matrix")
+    cap = packets.shape[0]
+    _check_i32(cap, reply_len=reply_len)
+    _check_i64(2, reply_counts=reply_counts)
+    if reply_len is None or reply_counts is None:
+        raise ValueError("reply_len and reply_counts are required")
+    _native.check(_native.load().rt_reply_remember(lst, _p(packets), LINE, _p(reply_len), _p(reply_counts), cap,
+                                                   _stream(stream, packets.device)))
 
 
 def packet_unpack(pkt, pkt_off, pkt_len, fields, stream=None):

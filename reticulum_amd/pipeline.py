@@ -26,6 +26,10 @@ Inbound, as the interface's read loop hands frames to Transport:
                              (with accept, between the filter and the dispatch)
     packets for the node's   Transport.py:2188-2202, Identity.py:848-898, 942-953
     SINGLE destinations      (with deliver: opened and proved, after the decrypt)
+    replies sent             Transport.py:1069-1104, 1199-1356, 1343-1345 (with
+                             reply, or pipeline.reply on the result: the rows of
+                             accept, signers and deliver gathered, signed, masked
+                             and framed for the socket the read came from)
 
 Every stage is one of reticulum_amd.device's kernels, the rearranging of
 offsets and lengths between them included (frames_compact, token_spans), and
@@ -134,10 +138,113 @@ def outbound(ks: KeySet, pt, iv, destination_hash, context, ifac=None, ifac_key=
     return framed, frame_off
 
 
+# The sources of a read's replies, in the order the reply stage numbers them
+# (device.REPLY_LRPROOF, REPLY_LINK_PROOF, REPLY_DEST_PROOF): the rows of
+# ``accept``, ``signers`` and ``deliver`` with their length columns.
+REPLY_SOURCES = (("lr_proofs", "lr_proof_len"), ("proofs", "proof_len"), ("dest_proofs", "dest_proof_len"))
+
+
+def _check_reply_ifac(ifac_key, ifac_size):
+    if not 0 <= int(ifac_size) <= 64:
+        raise ValueError("ifac_size must be 0..64")
+    if ifac_size and (ifac_key is None or ifac_key.numel() != 64):
+        raise ValueError("the access code is signed with a 64-byte ifac_key (Identity.from_bytes)")
+
+
+def reply(res, ifac_key=None, ifac_size=0, max_replies=None, seen=None, stream=None):
+    """The send side of a read: what ``inbound`` left to be transmitted, as the
+    framed byte stream for the socket the read came from.  ``res`` is an
+    ``inbound`` result (or any dict of the same columns); of ``lr_proofs``,
+    ``proofs`` and ``dest_proofs`` (each with its length column) the ones
+    present are the sources, numbered in that fixed order whichever are there
+    (device.REPLY_LRPROOF, REPLY_LINK_PROOF, REPLY_DEST_PROOF).  The reference
+    sends each of these packets on the interface its frame came in on, in the
+    order of its loop over the frames (Identity.py:942-953, Link.py:366-389,
+    Transport.py:1199-1356), so the replies are ordered by frame, then by
+    source.
+
+    The rows are gathered (device.reply_gather); with ``ifac_size`` > 0 every
+    reply gets its access code and is masked under the 64-byte ``ifac_key``
+    (device.ifac_sign, ifac_mask; Transport.py:1069-1101), without it the
+    packets go out as packed (:1104); the result is framed by
+    device.hdlc_frame_counted, which takes the number of replies from the
+    device.  With ``seen`` (a :class:`reticulum_amd.filter.PacketHashlist`) the
+    packet hashes of the replies enter the list, as Transport.outbound does for
+    what it broadcasts (Transport.py:1343-1345): an echo of the node's own
+    reply is then dropped as a replay.
+
+    Returns a dict of device tensors: ``stream`` (uint8) and ``frame_off``
+    ((max_replies + 1,) int64): the bytes to send are
+    stream[:frame_off[max_replies]], reply j at stream[frame_off[j]:
+    frame_off[j + 1]]; ``reply_counts`` ((2,) int64: [written, found]),
+    ``reply_frame`` and ``reply_len`` (int32), ``reply_source`` (uint8) and
+    ``packets`` ((max_replies, 128) uint8: the raw replies).  ``max_replies``
+    defaults to the number of frames, one reply per frame, which is what the
+    stages of ``inbound`` can produce; replies beyond it (found > written) stay
+    with the caller.  Nothing is synchronised, except that the interface
+    identity's public key is computed once per ``ifac_key`` and device
+    (:func:`ifac_identity`)."""
+    have = [k for k, (rows, ln) in enumerate(REPLY_SOURCES) if res.get(rows) is not None and res.get(ln) is not None]
+    if not have:
+        raise ValueError("reply needs at least one of lr_proofs, proofs and dest_proofs with its length column "
+                         "(inbound with accept, signers or deliver)")
+    _check_reply_ifac(ifac_key, ifac_size)
+    # the source index is the stage's, so absent stages before a present one are empty sources
+    first = res[REPLY_SOURCES[have[0]][0]]
+    n, dev = first.shape[0], first.device
+    cap = n if max_replies is None else int(max_replies)
+    if cap < 0:
+        raise ValueError("max_replies must be >= 0")
+    if ifac_size:
+        seed, pub = ifac_identity(ifac_key)
+    with _on(stream):      # temporaries allocated on the stream that uses them
+        sources = []
+        nothing = None
+        for k in range(have[-1] + 1):
+            if k in have:
+                sources.append((res[REPLY_SOURCES[k][0]], res[REPLY_SOURCES[k][1]]))
+            else:
+                if nothing is None:
+                    nothing = (torch.empty((n, 1), dtype=torch.uint8, device=dev),
+                               torch.zeros(n, dtype=torch.int32, device=dev))
+                sources.append(nothing)
+        packets = torch.empty((cap, device.LINE), dtype=torch.uint8, device=dev)      # the allocator's blocks start on a line
+        reply_len = torch.empty(cap, dtype=torch.int32, device=dev)
+        reply_frame = torch.empty(cap, dtype=torch.int32, device=dev)
+        reply_source = torch.empty(cap, dtype=torch.uint8, device=dev)
+        reply_counts = torch.empty(2, dtype=torch.int64, device=dev)
+        device.reply_gather(sources, packets, reply_len, reply_frame, reply_source, reply_counts, stream=stream)
+        if seen is not None:
+            device.reply_remember(seen.handle, packets, reply_len, reply_counts, stream=stream)
+        flat = packets.view(-1)
+        # every entry's offset lies inside its buffer, the empty ones past the
+        # replies included: ifac_mask reads a length-0 entry's two header bytes
+        p_off = torch.arange(cap, dtype=torch.int64, device=dev) * device.LINE
+        if ifac_size:
+            ml = device.LINE + ifac_size
+            ifac = torch.empty((cap, ifac_size), dtype=torch.uint8, device=dev)
+            device.ifac_sign(seed, pub, flat, p_off, reply_len, ifac, stream=stream)
+            masked = torch.empty(max(cap * ml, 1), dtype=torch.uint8, device=dev)
+            m_off = torch.arange(cap, dtype=torch.int64, device=dev) * ml
+            device.ifac_mask(flat, p_off, reply_len, ifac, ifac_key, masked, m_off, stream=stream)
+            m_len = reply_len + ifac_size      # past the replies: not a length, and not read as one
+        else:
+            # an interface without IFAC transmits the packet as packed (Transport.py:1104)
+            ml, masked, m_off, m_len = device.LINE, flat, p_off, reply_len
+        framed = torch.empty(max(cap * (2 * ml + 2), 1), dtype=torch.uint8, device=dev)
+        frame_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+        device.hdlc_frame_counted(masked, m_off, m_len, reply_counts, framed, frame_off, stream=stream)
+    return {"stream": framed, "frame_off": frame_off, "reply_counts": reply_counts, "reply_frame": reply_frame,
+            "reply_source": reply_source, "reply_len": reply_len, "packets": packets}
+
+
+_reply = reply             # inbound's ``reply`` argument hides the name
+
+
 def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stream=None, aligned=None,
             check_ifac=False, links=None, seen=None, transport_identity=None, transit=None, announces=False,
             signers=None, receipts=None, accept=None, establish=None, deliver=None,
-            implicit_proof=True, destination_receipts=None):
+            implicit_proof=True, destination_receipts=None, reply=None):
     """One read of an interface's byte stream ``buf`` (uint8 on the device)
     through deframing, IFAC unmask (skipped for ``ifac_size`` 0, an interface
     without access codes: then frames with the IFAC flag set are dropped, as
@@ -238,9 +345,8 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     result gains ``proofs`` (uint8, max_pairs x 128: the 115-byte LINK PROOF
     packet where ``proof_len`` is 115) and ``proof_len`` (int32 per frame, 115
     or 0).  A packet an earlier stage dropped is neither proved nor settled.
-    The proof rows are raw packets: compacting them by ``proof_len`` and
-    sending them (ifac_sign, ifac_mask, hdlc_frame) is the caller's part, and
-    so are links that prove by callback (PROVE_APP: flags 0, the caller signs
+    The proof rows are raw packets: ``reply`` sends them.  The caller's part
+    are links that prove by callback (PROVE_APP: flags 0, the caller signs
     the ``packet_hash`` column of ``fields`` with device.ed25519_sign).
 
     ``accept`` answers the link requests of the read that are addressed to the
@@ -265,8 +371,7 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     frame, device.LINKREQ_*), ``accepted_link`` (int32: the slot or -1),
     ``link_id`` (uint8, max_pairs x 16) and ``link_mtu`` (int32) for every valid
     request, ``lr_proofs`` (uint8, max_pairs x 128: the 118-byte LRPROOF packet
-    where ``lr_proof_len`` is 118) and ``lr_proof_len``.  Sending the rows and
-    the links' host state (watchdog, timeouts, callbacks, the LRRTT that
+    where ``lr_proof_len`` is 118) and ``lr_proof_len`` (``reply`` sends the rows).  The links' host state (watchdog, timeouts, callbacks, the LRRTT that
     activates the link) stay with the caller, keyed by the slot.  Out of scope:
     the initiator side, requests in transit for other nodes, PROVE_APP and the
     per-interface ingress limits.
@@ -307,8 +412,9 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     without) and ``dest_proof_len``; ``pt_off``, ``pt_len`` and ``status``
     become valid for the DELIVERED and NOT_OPENED frames.  GROUP and PLAIN
     destinations, the PROVE_APP callback (its frames are delivered, not
-    proved), the ratchet reload-and-retry, ratchet rotation, DEFERRED frames,
-    sending the proof rows and the receive callbacks stay with the caller.
+    proved), the ratchet reload-and-retry, ratchet rotation, DEFERRED frames
+    and the receive callbacks stay with the caller; ``reply`` sends the proof
+    rows.
 
     ``destination_receipts`` (a
     :class:`reticulum_amd.proof.DestinationReceipts`) settles the proofs of the
@@ -322,7 +428,26 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     ``dproof_status`` (int32 per frame, device.DPROOF_*) and ``dproof_receipt``
     (int32: the delivered receipt's id, which has left the table, or -1).  The
     reverse-table transport of proofs, timeouts, culling, delivery callbacks
-    and DPROOF_DEFERRED frames stay with the caller."""
+    and DPROOF_DEFERRED frames stay with the caller.
+
+    ``reply`` (True, or a dict with ``max_replies``) sends what the read
+    produced: at the end of the read the rows of ``accept``, ``signers`` and
+    ``deliver`` (at least one of them is needed) go through :func:`reply` with
+    the read's own ``ifac_key``, ``ifac_size`` and ``seen``, and the result
+    gains ``reply``, that function's dict: ``reply["stream"][:reply["frame_off"]
+    [-1]]`` is what goes back on the socket.  Without the argument the read
+    makes exactly the calls it makes without it."""
+    if reply is not None and reply is not False:
+        if reply is not True and not isinstance(reply, dict):
+            raise ValueError("reply is True or a dict with max_replies")
+        if signers is None and accept is None and deliver is None:
+            raise ValueError("reply needs at least one of signers, accept and deliver: the stages that write replies")
+        reply_args = {} if reply is True else dict(reply)
+        if set(reply_args) - {"max_replies"}:
+            raise ValueError("reply takes max_replies only")
+        _check_reply_ifac(ifac_key, ifac_size)
+    else:
+        reply_args = None
     if deliver is not None and (links is None or max_pairs > deliver.max_frames):
         raise ValueError("deliver needs links (an empty table will do) and max_pairs <= deliver.max_frames")
     if establish is not None and (links is None or ks.key_len != 64):
@@ -479,6 +604,8 @@ def inbound(ks: KeySet, buf, ifac_key, ifac_size, max_pairs, hw_mtu=262144, stre
     if deliver is not None:
         res.update(deliver_status=deliver_status, destination=destination, ratchet=ratchet, dest_proofs=dest_proofs,
                    dest_proof_len=dest_proof_len)
+    if reply_args is not None:
+        res["reply"] = _reply(res, ifac_key=ifac_key, ifac_size=ifac_size, seen=seen, stream=stream, **reply_args)
     return res
 
 

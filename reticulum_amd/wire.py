@@ -301,6 +301,80 @@ def transmit_batch(raws, ifac_size, ifac_key, device=None):
     return [out[int(o):int(o) + int(l)] for o, l in zip(out_off, out_len)]
 
 
+def reply_batch(rows_by_source, ifac_key=None, ifac_size=0, device=None):
+    """The replies of one read as the byte stream for its socket, from host
+    bytes (pipeline.reply without tensors).  ``rows_by_source`` holds one to
+    four sources over the same n frames, each a sequence of n entries: the
+    reply packet (1..128 bytes) that source has for the frame, or None / b""
+    for nothing.  The replies go out ordered by frame, then by source
+    (rt_reply_gather); with ``ifac_size`` > 0 each is signed and masked under
+    the 64-byte ``ifac_key`` (Transport.py:1069-1101), else sent as packed; all
+    are HDLC-framed (rt_hdlc_frame_counted).  Returns (stream bytes,
+    reply_frame, reply_source): the frame and the source index of each reply
+    in the stream, as int32 / uint8 arrays."""
+    srcs = [list(src) for src in rows_by_source]
+    S = len(srcs)
+    if not 1 <= S <= 4:
+        raise ValueError("reply_batch takes 1 to 4 sources")
+    n = len(srcs[0])
+    if any(len(src) != n for src in srcs):
+        raise ValueError("every source has one entry per frame")
+    size = _check_ifac_size(ifac_size, ifac_key) if ifac_size else 0
+    mats, lens = [], []
+    for src in srcs:
+        m, ln = np.zeros((max(n, 1), 128), np.uint8), np.zeros(max(n, 1), np.int32)
+        for k, row in enumerate(src):
+            if row is None:
+                continue
+            _check_bytes(row, "reply")
+            if len(row) > 128:
+                raise ValueError("a reply is at most 128 bytes")
+            m[k, :len(row)] = np.frombuffer(bytes(row), np.uint8)
+            ln[k] = len(row)
+        mats.append(m)
+        lens.append(ln)
+    cap = n * S
+    if cap == 0:
+        return b"", np.zeros(0, np.int32), np.zeros(0, np.uint8)
+    ml = 128 + size
+    with _Dev(device) as d:
+        lib = d.lib
+        c_rows = (ctypes.c_void_p * S)(*[d.up(m) for m in mats])
+        c_len = (ctypes.c_void_p * S)(*[d.up(ln) for ln in lens])
+        c_stride = (ctypes.c_uint64 * S)(*[128] * S)
+        c_width = (ctypes.c_uint32 * S)(*[128] * S)
+        # (the library's allocations start on a 256-byte boundary at least: the rows on a line)
+        p_out, p_len, p_frame, p_src = d.alloc(128 * cap), d.alloc(4 * cap), d.alloc(4 * cap), d.alloc(cap)
+        p_counts = d.alloc(16)
+        ws = d.alloc(lib.rt_reply_gather_workspace_bytes(n, S))
+        _native.check(lib.rt_reply_gather(d.ctx, S, c_rows, c_stride, c_width, c_len, n, p_out, p_len, p_frame, p_src,
+                                          p_counts, cap, ws, None))
+        p_off = d.up(np.arange(cap, dtype=np.uint64) * 128)
+        p_pkt, p_poff, p_plen = p_out, p_off, p_len
+        if size:
+            key = np.frombuffer(bytes(ifac_key), np.uint8)
+            p_seed, p_pub = _ifac_identity(d, ifac_key)
+            p_ifac = d.alloc(cap * size)
+            p_pkt = d.alloc(cap * ml)
+            p_poff = d.up(np.arange(cap, dtype=np.uint64) * ml)
+            _native.check(lib.rt_ifac_sign(d.ctx, p_seed, p_pub, p_out, p_off, p_len, p_ifac, size, cap, None))
+            _native.check(lib.rt_ifac_mask(d.ctx, p_out, p_off, p_len, p_ifac, size, d.up(key), len(key), p_pkt,
+                                           p_poff, cap, None))
+            # the masked lengths of the replies; the entries past them are not counted
+            p_plen = d.up(d.down(p_len, np.zeros(cap, np.int32)) + size)
+        p_stream = d.alloc(cap * (2 * ml + 2))
+        p_foff = d.alloc(8 * (cap + 1))
+        fws = d.alloc(lib.rt_hdlc_frame_workspace_bytes(cap))
+        _native.check(lib.rt_hdlc_frame_counted(d.ctx, p_pkt, p_poff, p_plen, cap, p_counts, p_stream, p_foff, fws,
+                                                None))
+        foff = d.down(p_foff, np.zeros(cap + 1, np.uint64))
+        written = int(d.down(p_counts, np.zeros(2, np.int64))[0])
+        out = d.down(p_stream, np.zeros(int(foff[-1]), np.uint8))
+        frames = d.down(p_frame, np.zeros(cap, np.int32))[:written]
+        sources = d.down(p_src, np.zeros(cap, np.uint8))[:written]
+    return out.tobytes(), frames, sources
+
+
 def receive_batch(raws, ifac_size, ifac_key, device=None):
     """Transport.inbound's IFAC block (Transport.py:1441-1480) for many
     received packets on an interface with IFAC: the reassembled packet that
