@@ -100,8 +100,14 @@ def expand(seed):
     return a, h[32:]
 
 
-def public_key(seed):
+@functools.lru_cache(maxsize=None)
+def _public_key(seed):
     return encode(mul(expand(seed)[0] % L, BASE))
+
+
+def public_key(seed):
+    """Remembered per seed: sign() without a public key derives it on every call."""
+    return _public_key(bytes(seed))
 
 
 def sign(seed, msg, pk=None):

@@ -16,9 +16,9 @@ import ed25519_ref as ed
 import ifac_helpers as ih
 import link_accept_helpers as la
 import link_helpers as lh
+import mixed_read_helpers as mr
 import proof_helpers as ph
 import reply_helpers as rh
-from oracle import ctoken
 from oracle import wire as ow
 
 pytestmark = pytest.mark.gpu
@@ -49,36 +49,17 @@ def _keyset(keys):
 
 @pytest.fixture(scope="module")
 def world():
-    """The node, its peer, and the read the peer sent."""
+    """The node, its peer, and the read the peer sent: made on the host
+    (mixed_read_helpers.reply_world, the link request included), so that the
+    composed model reads the same world; the peer's pending link is entered
+    from the host-made request."""
     import reticulum_amd as rt
-    rng = np.random.Generator(np.random.PCG64(1069))
-    w = dict(rng=rng, ifac_key=_rb(rng, 64), tid=_rb(rng, 16), peer_tid=_rb(rng, 16))
-    keys = [_rb(rng, 64) for _ in range(N_KEYS)]
-    link_ids = [_rb(rng, 16), _rb(rng, 16)]
-    seeds = [_rb(rng, 32) for _ in range(N_KEYS)]                   # the node's signing seeds, by row
-    dests = [dd.make_dest(rng, 0, dd.F_PROVE_ALL), dd.make_dest(rng, 2, dd.F_PROVE_ALL)]
-    # the peer opens a link to destination 1 of the node: the request, and the pending link on its side
+    w = mr.reply_world()
+    o = w["opened"]
     pending = rt.PendingLinks(8, device=0)
-    (request,), (link_id,) = rt.open_requests_batch([dests[1].hash], [ed.public_key(dests[1].seed)], [_rb(rng, 32)],
-                                                    [_rb(rng, 32)], [PEER_SLOT], [1], mtu=500, pending=pending)
-
-    def link_data(k, text):
-        return bytes([lh.LINK << 2 | lh.DATA, 0]) + link_ids[k] + b"\x00" + ctoken.encrypt(keys[k], _rb(rng, 16), text)
-
-    def single(k, rank, text):
-        return dd.packet(dd.seal(dests[k], rank, text, _rb(rng, 32), _rb(rng, 16)), dests[k].hash)
-
-    frames = [
-        ("link 0", link_data(0, b"on link 0")),
-        ("noise", bytes([lh.LINK << 2 | lh.DATA, 0]) + _rb(rng, 16) + b"\x00" + _rb(rng, 70)),
-        ("single 0", single(0, None, b"to destination 0")),
-        ("request", request),
-        ("link 1", link_data(1, b"on link 1")),
-        ("single 1", single(1, 0, b"by the newest ratchet")),
-        ("more noise", _rb(rng, 40)),
-        ("link 0 again", link_data(0, b"and one more")),
-    ]
-    w.update(keys=keys, link_ids=link_ids, seeds=seeds, dests=dests, pending=pending, link_id=link_id, frames=frames)
+    assert pending.add([o.link_id], [o.prv], [o.dest_public], [o.sig_seed], [o.flags], [o.slot],
+                       [o.expected_hops]).tolist() == [0]
+    w["pending"] = pending
     return w
 
 
@@ -89,14 +70,11 @@ def _node_read(w, seen, reply, buf=None):
     d, frames = w["dests"], w["frames"]
     tab = rt.LinkTable(32, device=0)
     assert tab.insert(w["link_ids"], [0, 1]).cpu().tolist() == [lh.OK] * 2
-    flags = [ph.PROVE_ALL, ph.PROVE_ALL] + [0] * (N_KEYS - 2)
-    signers = rt.LinkSigners(w["seeds"], [_rb(np.random.Generator(np.random.PCG64(k)), 32) for k in range(N_KEYS)],
-                             flags, device=0)
+    signers = rt.LinkSigners(w["seeds"], w["peer_publics"], w["flags"], device=0)
     accept = dict(destinations=rt.LinkDestinations([x.hash for x in d], [x.seed for x in d], [la.F_ACCEPTS] * len(d),
                                                    device=0),
                   slots=_t(np.array([SLOT, SLOT + 1], np.int32)), nh_mtu=500,
-                  ephemeral_privates=_t(np.frombuffer(_rb(np.random.Generator(np.random.PCG64(77)), 64),
-                                                      np.uint8).reshape(2, 32)))
+                  ephemeral_privates=_t(np.frombuffer(b"".join(w["ephemerals"]), np.uint8).reshape(2, 32)))
     deliver = rt.SingleDestinations([x.hash for x in d], [x.prv for x in d], [x.identity_hash for x in d],
                                     [x.seed for x in d], [x.flags for x in d], [x.ratchets for x in d],
                                     max_frames=64, retry_trials=32, device=0)
@@ -138,7 +116,16 @@ def test_one_mixed_read_and_the_loop_it_closes(world):
     assert res["proof_len"][:8].cpu().tolist() == [115, 0, 0, 0, 115, 0, 0, 115]
     assert res["lr_proof_len"][:8].cpu().tolist() == [0, 0, 0, 118, 0, 0, 0, 0]
     assert res["dest_proof_len"][:8].cpu().tolist() == [0, 0, 83, 0, 0, 83, 0, 0]
+    # and all of it as the composed model has it, row for row: nothing of the device's enters this expectation
+    model = mr.compose(mr.reply_node(w), mr.reply_wire(w), ISZ, 32)
+    for rows, ln in pipeline.REPLY_SOURCES:
+        assert res[ln].cpu().tolist() == mr.lengths(model[rows]), ln
+        for i, row in enumerate(model[rows]):
+            assert row is None or res[rows][i, :len(row)].cpu().numpy().tobytes() == row, (rows, i)
     rep = res["reply"]
+    assert [(k, s) for k, s, _ in model["replies"]] == list(zip(rep["reply_frame"][:6].cpu().tolist(),
+                                                                 rep["reply_source"][:6].cpu().tolist()))
+    assert bytes(rep["stream"][:int(rep["frame_off"][32])].cpu().numpy()) == b"".join(model["reply_frames"])
     assert set(rep) == {"stream", "frame_off", "reply_counts", "reply_frame", "reply_source", "reply_len", "packets"}
     replies, found = _model_over(res)
     assert found == 6 and rep["reply_counts"].cpu().tolist() == [6, 6]
